@@ -9,10 +9,20 @@ One step = forward (train mode, dropout 0.7 active) -> CrossEntropy(one-hot)
 -> backward -> gradient all-reduce over ranks (RCCL, N > 1) -> Lookahead(RAdam)
 optimizer step -> zero_grad.  Bags are resident in HBM before timing starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 8192] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU)
 
-Prints ONE JSON line on rank 0.  Extra objects:
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps, writes the
+last timed step's outputs (--dump-outputs) and prints the line; its extra objects are null.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last timed step computed as
+DIR/<name>.npy (float32): loss, y_prob, y_hat of that micro-batch, every parameter after it
+(param.<name>) and the gradients it left in the bucket (grad.<name>); at most 64 MB in all (a
+larger array is stored as a fixed, seeded sample of its elements).  Weights, bags and dropout
+seeds are seeded, so two runs with the same arguments see identical inputs.
+
+--full adds the measurements that take runs of their own (after the timed region and the dump).
+Extra objects:
   roofline      -- the dominant kernel's achieved rate: by default the pseudo-inverse
                    forward chain (tm_pinv_fwd_split: 14 launches of pinv_stage_kernel, the
                    largest share of the step in profiles/r02_*_kernel_summary.txt), its
@@ -75,6 +85,11 @@ def parse():
     ap.add_argument("--no-cpu-as-written", action="store_true",
                     help="skip the CPU oracle timed as the reference is written (the n'xn' return_attn product)")
     ap.add_argument("--no-hbm-probe", action="store_true", help="skip the per-kernel HBM roofline list")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the roofline probes, the optimizer "
+                         "timing and the CPU baselines (the --no-* / --probe / --cpu-* options select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -366,8 +381,9 @@ def make_step(task, opt, allreduce, bags, labels, K, warmup, eager=False):
     added, all-reduced, optimizer step), one captured graph per (bag, phase).  Warm-up: warmup * K
     eager micro-batches (at least 2 K) on a side stream before the captures, then every captured
     graph replayed once (micro-batches 0 .. len(bags) * K - 1).  Returns a namespace with ``step``,
-    ``body(x, y, phase)``, ``load(i)``, ``graph`` (None when eager) and ``warm_micro`` = (eager
-    warm-up micro-batches, warm-up replays)."""
+    ``body(x, y, phase)``, ``load(i)``, ``graph`` (None when eager), ``warm_micro`` = (eager
+    warm-up micro-batches, warm-up replays) and ``outputs(i)``: the loss / y_prob / y_hat tensors
+    micro-batch i wrote (valid once ``step(i)`` was the last step run)."""
     static_x = torch.empty_like(bags[0])
     static_y = torch.empty_like(labels[0])
 
@@ -388,8 +404,14 @@ def make_step(task, opt, allreduce, bags, labels, K, warmup, eager=False):
         static_x.copy_(bags[i % len(bags)])
         static_y.copy_(labels[i % len(bags)])
 
+    def step_outputs():
+        return dict(loss=task._last_loss, y_prob=task._last_outputs[0], y_hat=task._last_outputs[1])
+
     graph = None
     if eager:
+        def outputs(i):
+            return step_outputs()   # the task holds the last micro-batch's
+
         def step(i):
             load(i)
             body(phase=phase_of(i))
@@ -411,7 +433,7 @@ def make_step(task, opt, allreduce, bags, labels, K, warmup, eager=False):
         # one captured step per resident bag (reading that bag in place: no copy into a static
         # input inside the timed region), all on one memory pool -- they never run at once
         pool = torch.cuda.graph_pool_handle()
-        graphs = {}
+        graphs, held = {}, {}
         phases = ["last"] if K == 1 else (["first", "mid", "last"] if K > 2 else ["first", "last"])
         for j in range(len(bags)):
             opt.zero_grad(set_to_none=True)   # the first capture takes the first-micro-batch (=) path,
@@ -420,7 +442,11 @@ def make_step(task, opt, allreduce, bags, labels, K, warmup, eager=False):
                 with torch.cuda.graph(gj, pool=pool):
                     body(bags[j], labels[j], phase=ph)
                 graphs[j, ph] = gj
+                held[j, ph] = step_outputs()   # this graph's own output tensors, kept out of the pool's reuse
         graph = graphs[0, "last"]
+
+        def outputs(i):
+            return held[i % len(bags), phase_of(i)]
 
         def step(i):
             graphs[i % len(bags), phase_of(i)].replay()
@@ -432,8 +458,26 @@ def make_step(task, opt, allreduce, bags, labels, K, warmup, eager=False):
         for i in range(len(bags) * K):
             step(i)
         torch.cuda.synchronize()
-    return types.SimpleNamespace(step=step, body=body, load=load, graph=graph, phase_of=phase_of,
+    return types.SimpleNamespace(step=step, body=body, load=load, graph=graph, phase_of=phase_of, outputs=outputs,
                                  warm_micro=(max(warmup, 2) * K, 0 if eager else len(bags) * K))
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, named):
+    """``named``: (name, tensor) pairs -> path/<name>.npy, float32.  Every array gets an equal share
+    of the budget; one above its share is stored as a sample of its flattened elements at sorted
+    indices drawn without replacement from numpy's default_rng(0) (the same ones every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    named = list(named)
+    share = DUMP_BUDGET_BYTES // (4 * max(len(named), 1))
+    for name, t in named:
+        a = t.detach().to("cpu", torch.float32).numpy().copy()
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def main():
@@ -477,7 +521,11 @@ def main():
 
     # the roofline call site, and the pseudo-inverse backward beside the forward chain
     probe_sites = {args.probe, "pinv_bwd"} if args.probe == "pinv_fwd" else {args.probe}
-    if args.eager:
+    if not args.full:
+        # a plain run: the timed steps alone (the probes, the optimizer timing and the CPU
+        # baselines below each take runs of their own)
+        args.no_hbm_probe = args.no_cpu_baseline = True
+    if args.eager and args.full:
         engine.probe.target = probe_sites
         engine.probe.events.clear()
         engine.probe.names.clear()
@@ -501,7 +549,13 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
-    if graph is not None:
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # before anything below runs further steps: the last timed micro-batch's results
+        last = st.outputs(args.steps - 1)
+        params = [(n.replace("/", "_"), p) for n, p in model.named_parameters()]
+        dump_outputs(args.dump_outputs, list(last.items()) + [("param." + n, p) for n, p in params]
+                     + [("grad." + n, p.grad) for n, p in params if p.grad is not None])
+    if graph is not None and args.full:
         # after the timed region: the same step captured once more with external HIP events
         # around the probed launches (graph event-record nodes on the kernel's stream), replayed
         # three times; the events hold each replay's timestamps.  The timed graph has no probes.
@@ -561,7 +615,7 @@ def main():
     # the optimizer step alone (it is also inside every timed step): a graph of opt.step()
     # replayed 20 times between two events (after the timed region; it advances the state)
     opt_ms = None
-    if graph is not None:
+    if graph is not None and args.full:
         try:
             og = torch.cuda.CUDAGraph()
             with torch.cuda.graph(og):
@@ -634,6 +688,7 @@ def main():
                        "accumulate_grad_batches": K},
             "roofline": roof,
             "roofline_pinv_bwd": roofline_obj("pinv_bwd") if args.probe == "pinv_fwd" else None,
+            "full": args.full,
             "hbm_roofline": hbm,
             "gemm_roofline": gemms,
             "optimizer_ms": round(opt_ms, 5) if opt_ms is not None else None,

@@ -3,7 +3,7 @@
 # time limit; the first failing stage ends the script (no retries).  Outputs under gpurun_out/$TAG/.
 #   tests    pytest -m gpu (TESTS= to select)                 -> gpu_tests.txt
 #   smoke    __graft_entry__.smoke()                            -> smoke.txt
-#   bench    bench.py (BENCH_ARGS=, default: no CPU baseline)  -> bench.log
+#   bench    bench.py (BENCH_ARGS=, default: --full, no CPU baseline)  -> bench.log
 #   prof     rocprofv3 --kernel-trace --stats of the bench      -> prof/
 #   c5drift  scripts/dev/c5_drift.py under a kernel trace       -> c5_drift.json, c5drift_prof/
 #   c5       scripts/bench_c5.py (C5_ARGS=)                      -> c5.log
@@ -31,11 +31,11 @@ for S in ${STAGES:-tests bench}; do
       run smoke 300 bash -c "python -u -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")' > $OUT/smoke.txt 2>&1"
       tail -1 "$OUT/smoke.txt" ;;
     bench)
-      run bench 600 bash -c "python -u bench.py ${BENCH_ARGS:---no-cpu-baseline --no-cpu-as-written} > $OUT/bench.log 2>&1"
+      run bench 600 bash -c "python -u bench.py ${BENCH_ARGS:---full --no-cpu-baseline --no-cpu-as-written} > $OUT/bench.log 2>&1"
       tail -1 "$OUT/bench.log" | cut -c1-300 ;;
     prof)
       run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-        python3 bench.py --no-cpu-baseline --no-cpu-as-written --steps ${PROF_STEPS:-200} > "$OUT/prof_bench.log" 2>&1
+        python3 bench.py --full --no-cpu-baseline --no-cpu-as-written --steps ${PROF_STEPS:-200} > "$OUT/prof_bench.log" 2>&1
       tail -1 "$OUT/prof_bench.log" | cut -c1-200 ;;
     c5drift)
       run c5drift 600 rocprofv3 --kernel-trace --stats -d "$OUT/c5drift_prof" -o run --output-format csv -- \

@@ -3,7 +3,7 @@
 # step ends the script (no retries):
 #   1. the GPU test suite            -> gpurun_out/final/gpu_tests.txt
 #   2. __graft_entry__.smoke()       -> gpurun_out/final/smoke.txt
-#   3. bench.py as the driver runs it (default flags: CPU baselines + hbm_roofline probe)
+#   3. bench.py --full (default sizes: the roofline probes + CPU baselines beside the timed steps)
 #                                    -> gpurun_out/final/bench.log
 #   3b. bench.py --gpus 1 --steps 20 --warmup 5 (the driver's exact command)
 #                                    -> gpurun_out/final/bench_driver_cmd.log
@@ -27,7 +27,7 @@ timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('s
 rc=$?; tail -2 "$OUT/smoke.txt"
 [ $rc -eq 0 ] || { echo "smoke rc=$rc: stopping"; exit $rc; }
 step bench
-timeout -k 10 600 python -u bench.py > "$OUT/bench.log" 2>&1
+timeout -k 10 600 python -u bench.py --full > "$OUT/bench.log" 2>&1
 rc=$?; tail -1 "$OUT/bench.log" | cut -c1-200
 [ $rc -eq 0 ] || { echo "bench rc=$rc: stopping"; exit $rc; }
 step bench-driver-command
@@ -36,7 +36,7 @@ rc=$?; tail -1 "$OUT/bench_driver_cmd.log" | cut -c1-200
 [ $rc -eq 0 ] || { echo "bench (driver command) rc=$rc: stopping"; exit $rc; }
 step rocprof
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-  python3 bench.py --no-cpu-baseline --no-cpu-as-written > "$OUT/prof_bench.log" 2>&1
+  python3 bench.py --full --no-cpu-baseline --no-cpu-as-written > "$OUT/prof_bench.log" 2>&1
 rc=$?; tail -1 "$OUT/prof_bench.log" | cut -c1-200
 [ $rc -eq 0 ] || { echo "rocprof rc=$rc: stopping"; exit $rc; }
 step pmc
