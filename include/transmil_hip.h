@@ -170,7 +170,6 @@ int tm_nys_a3_fwd_sim2(const float* ql, const float* kl, const void* k, const vo
 /* merged[b][t][head*64+d] = softmax(q kl^T) y + conv33(v); lse1 [B*h, n]; kl_t, y_t: T copies */
 int tm_nys_a1_fwd(int dtype, const void* q, const void* v, const void* kl_t, const void* y_t,
                   const float* wconv, int nbh, int nh, int n, void* merged, float* lse1, void* stream);
-int tm_nys_rowdot_cast(int dtype, const float* dw, const float* w, int rows, float* dd, void* dw_t, void* stream);
 int tm_cast_f32(int dtype, const float* x, void* y, long long count, void* stream);
 long long tm_nys_conv_bwd_workspace(int nbags, int nh, int n);
 /* dv [B*h, n, 64] in the step's dtype T (bf16 in the bf16 mode: the fused A3 backward reads it once) */
@@ -203,8 +202,8 @@ int tm_nys_attn_row(int dtype, const void* q, const void* k, const float* ql, co
 int tm_nys_assemble_dqkv(int dtype, const float* dq, const float* dql, const float* dk, const float* dkl,
                          const float* dv, int nbags, int nh, int n, float scale, void* dqkv, void* stream);
 /* bf16 mode, fused key side: the A3 backward writes the final bf16 k / v parts of dqkv
- * (k = dK + dk~[t/l]/l, v = dv_conv + dV) and dql (=) from its slabs; then tm_nys_assemble_q
- * writes the q part, scale * (dq + (dql_a + dql_b)[t/l]/l).  dv_conv (bf16, as tm_nys_conv_bwd /
+ * (k = dK + dk~[t/l]/l, v = dv_conv + dV) and dql (=) from its slabs; then tm_nys_assemble_q_slab
+ * writes the q part, scale * (dq + (dql + sum_p slab[p])[t/l]/l).  dv_conv (bf16, as tm_nys_conv_bwd /
  * tm_cls_a1_row_bwd write it in the bf16 mode) is read only for rows
  * [dv_lo, dv_hi) (zero elsewhere; 0, n = dense); dq_row >= 0: dq is zero outside that row.
  * dql = NULL: the dq~ partial slab is left in work ([tm_nys_a3_bwd_slabs][B*h][256][64] bf16, each
@@ -214,8 +213,6 @@ int tm_nys_a3_bwd_fused(const void* ql_t, const void* dw_t, const void* k, const
                         const float* d3, int nbh, int nh, int n, const void* dv_conv, int dv_lo, int dv_hi,
                         const float* dkl, float* work, float* dql, void* dqkv, tm_reduce_queue* rq,
                         void* stream);
-int tm_nys_assemble_q(int dtype, const float* dq, int dq_row, const float* dql_a, const float* dql_b, int nbags,
-                      int nh, int n, float scale, void* dqkv, void* stream);
 /* partial slabs the bf16 A3 backward writes (tm_nys_a3_bwd_fused's work) */
 int tm_nys_a3_bwd_slabs(int nbh, int n);
 /* q part of dqkv, scale * (dq + (dql + sum_p slab[p])[t/l]/l), the slab sum in the same launch

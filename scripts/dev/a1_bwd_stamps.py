@@ -1,6 +1,6 @@
 """Per-phase s_memtime stamps of the bf16 A1 backward (attn_bwd_bf16_kernel<A1, 8>) at the bench shape
-(diagnostic build; nys variant 33: slots 0 start, 1 loads issued, 2 operands staged, 3 after query
-chunk 0, 4 after chunk 3, 5 after the query walk, 6 end (slab epilogue done); variant 34: inside
+(diagnostic build; NYS_SEL stamp_a1_bwd: slots 0 start, 1 loads issued, 2 operands staged, 3 after query
+chunk 0, 4 after chunk 3, 5 after the query walk, 6 end (slab epilogue done); stamp_a1_bwd_chunk: inside
 query chunk 2: 0 chunk start, 1 S / dP / dV / dK done, 2 after barrier 1, 3 after the dS write +
 barrier 2, 4 dQ MFMAs + partials, 5 after barrier 3, 6 dq stored).  Prints mean / max cycle deltas
 over workgroups for waves 0 and 4, and the eager time per call of the plain kernel.
@@ -18,6 +18,8 @@ import numpy as np            # noqa: E402
 import torch                  # noqa: E402
 from transmil_deepgraft_amd import _lib                    # noqa: E402
 from transmil_deepgraft_amd.engine import _p, _stream      # noqa: E402
+sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
+from microbench import NYS_SEL  # noqa: E402  (the diagnostic build's named selectors)
 
 nh, n, B = 8, 8448, 1
 nbh = B * nh
@@ -36,8 +38,8 @@ dy = torch.empty(nbh, 256, 64, device=dev)
 f = lambda: _lib.call("tm_nys_a1_bwd_dqkv", _p(q), _p(dmerged), _p(kl), _p(y), _p(lse), _p(d1), nbh, nh, n, _p(dqkv),
                       C.c_float(0.125), _p(work), _p(dkl), _p(dy), None, _stream())
 L = _lib.lib()
-for var in [0] + [int(x) for x in (sys.argv[1:] or ["33", "34"])]:
-    L.tm_debug_set_nys_variant(var)
+for var in ["auto"] + (sys.argv[1:] or ["stamp_a1_bwd", "stamp_a1_bwd_chunk"]):
+    L.tm_debug_set_nys_sel(NYS_SEL[var])
     for _ in range(3):
         f()
     torch.cuda.synchronize()
@@ -45,9 +47,9 @@ for var in [0] + [int(x) for x in (sys.argv[1:] or ["33", "34"])]:
     for _ in range(50):
         f()
     torch.cuda.synchronize()
-    print(f"variant {var}: {(time.perf_counter() - t) / 50 * 1e6:.1f} us per call (eager, incl. the two slab reduces)",
+    print(f"{var}: {(time.perf_counter() - t) / 50 * 1e6:.1f} us per call (eager, incl. the two slab reduces)",
           flush=True)
-    if var not in (33, 34):
+    if var == "auto":
         continue
     nblk = 32 * nbh
     buf = (C.c_ulonglong * (512 * 8 * 8))()
@@ -58,4 +60,4 @@ for var in [0] + [int(x) for x in (sys.argv[1:] or ["33", "34"])]:
         d = np.diff(st, axis=1)
         print(f"  wave {w}: mean cycles per phase", [int(x) for x in d.mean(0)], " max", [int(x) for x in d.max(0)])
         print(f"     total mean {int((st[:, 6] - st[:, 0]).mean())} cycles; start spread {int(st[:, 0].max() - st[:, 0].min())}")
-L.tm_debug_set_nys_variant(0)
+L.tm_debug_set_nys_sel(NYS_SEL["auto"])

@@ -1,5 +1,5 @@
-"""Per-phase (A3_STAMPS=31: slots 0 chunk start, 1 S/dP/dV/dK done, 2 after barrier 1, 3 after the dS
-write + barrier 2, 4 dQ done, 5 after barrier 3, 6 dq~ partial stored) s_memtime stamps of the bf16 A3 backward at the bench shape (diagnostic build, variant 30):
+"""Per-phase (A3_STAMPS=stamp_a3_bwd_chunk: slots 0 chunk start, 1 S/dP/dV/dK done, 2 after barrier 1, 3 after the dS
+write + barrier 2, 4 dQ done, 5 after barrier 3, 6 dq~ partial stored) s_memtime stamps of the bf16 A3 backward at the bench shape (diagnostic build, NYS_SEL stamp_a3_bwd):
 slots 0 start, 1 loads issued, 2 operands staged, 3 after query chunk 0, 4 after chunk 3, 5 after
 the query walk, 6 end (key-side epilogue done).  Prints mean / max cycle deltas over workgroups (wave 0)."""
 import ctypes as C, os, sys, time
@@ -10,6 +10,8 @@ import torch
 from transmil_deepgraft_amd import _lib
 from transmil_deepgraft_amd._lib import BF16
 from transmil_deepgraft_amd.engine import _p, _stream
+sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
+from microbench import NYS_SEL  # noqa: E402  (the diagnostic build's named selectors)
 nbh, n = 8, 8448
 dev = "cuda"
 g = torch.Generator(device="cpu").manual_seed(1)
@@ -32,15 +34,15 @@ if os.environ.get("A3_FUSED", "1") == "1":   # the bench's form: bf16 k / v rows
 else:
     f = lambda: _lib.call("tm_nys_a3_bwd", BF16, _p(ql), _p(dw), _p(k), _p(v), _p(lse), _p(d), nbh, 8, n, _p(dk),
                           _p(dv), _p(work), _p(dql), 0, None, _stream())
-STV = int(os.environ.get("A3_STAMPS", "30"))   # 30: phases; 31: inside query chunk 2
-for var in (0, STV):
-    _lib.lib().tm_debug_set_variant(1, var)
+STV = os.environ.get("A3_STAMPS", "stamp_a3_bwd")   # phases; stamp_a3_bwd_chunk: inside query chunk 2
+for var in ("auto", STV):
+    _lib.lib().tm_debug_set_nys_sel(NYS_SEL[var])
     for _ in range(3): f()
     torch.cuda.synchronize()
     t = time.perf_counter()
     for _ in range(50): f()
     torch.cuda.synchronize()
-    print(f"variant {var}: {(time.perf_counter() - t) / 50 * 1e6:.1f} us per call (eager, incl. the dq~ reduce)", flush=True)
+    print(f"{var}: {(time.perf_counter() - t) / 50 * 1e6:.1f} us per call (eager, incl. the dq~ reduce)", flush=True)
 nblk = 32 * nbh
 buf = (C.c_ulonglong * (512 * 8 * 8))()
 _lib.call("tm_debug_a1_stamps", buf, 512 * 8 * 8)
@@ -50,4 +52,4 @@ for w in (0, 4):
     d = np.diff(st, axis=1)
     print(f"wave {w}: mean cycles per phase", [int(x) for x in d.mean(0)], " max", [int(x) for x in d.max(0)])
     print(f"   total mean {int((st[:, 6] - st[:, 0]).mean())} cycles; start spread {int(st[:, 0].max() - st[:, 0].min())}")
-_lib.lib().tm_debug_set_variant(1, 0)
+_lib.lib().tm_debug_set_nys_sel(NYS_SEL["auto"])

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of two environments on ONE box with the same tree: bench.py alternated, A = $AB_ENV_A, B = $AB_ENV_B
-# (e.g. AB_ENV_A="" AB_ENV_B="TM_GEMM_QKV_BIG=0")
+# (e.g. AB_ENV_A="" AB_ENV_B="TM_STEM_FUSED=0")
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 for i in $(seq ${AB_PAIRS:-4}); do

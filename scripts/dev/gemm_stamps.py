@@ -1,4 +1,4 @@
-"""Per-workgroup timeline of the 2-stage ring GEMM (variant 8 stamps) on the step's shapes."""
+"""Per-workgroup timeline of the 2-stage ring GEMM (GEMM_SEL stamp_ring) on the step's shapes."""
 import sys, os, ctypes
 sys.path.insert(0, os.getcwd())
 import numpy as np
@@ -6,6 +6,8 @@ import torch
 from transmil_deepgraft_amd import engine as E
 from transmil_deepgraft_amd._lib import BF16, F32
 from transmil_deepgraft_amd import _lib
+sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
+from microbench import GEMM_SEL  # noqa: E402  (the diagnostic build's named selectors)
 
 L = _lib.lib()
 dev = "cuda"
@@ -15,11 +17,11 @@ for name, M, N, K, bkn, cd in (("out", 8448, 512, 512, 0, F32), ("dmerged", 8448
     A = (torch.randn(M, K, device=dev) * 0.1).to(torch.bfloat16)
     Bm = ((torch.randn(K, N, device=dev) if bkn else torch.randn(N, K, device=dev)) * 0.1).to(torch.bfloat16)
     Cm = torch.empty(M, N, device=dev, dtype=torch.float32 if cd == F32 else torch.bfloat16)
-    L.tm_debug_set_variant(2, 8)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["stamp_ring"])
     for _ in range(4):
         E.gemm(A, Bm, Cm, M, N, K, lda=K, ldb=N if bkn else K, ldc=N, b_kn=bkn, dtype=BF16, c_dtype=cd)
     torch.cuda.synchronize()
-    L.tm_debug_set_variant(2, 0)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["auto"])
     nb = ((M + 127) // 128) * ((N + 127) // 128)
     buf = (ctypes.c_ulonglong * (nb * 8))()
     assert L.tm_debug_gemm_stamps(buf, nb * 8) == 0

@@ -1,4 +1,4 @@
-"""Per-workgroup timeline of the 2-stage ring GEMM (diagnostic build, variant 8 stamps) on the step's
+"""Per-workgroup timeline of the 2-stage ring GEMM (diagnostic build, GEMM_SEL stamp_ring) on the step's
 shapes WITH their real epilogues: QKV head-major scatter, to_out (fp32 + bias + dropout + residual +
 row map), _fc1 (bias + GELU + pre-activation + row map), dmerged (plain bf16).
 
@@ -18,6 +18,8 @@ sys.path.insert(0, os.getcwd())
 from transmil_deepgraft_amd import _lib                      # noqa: E402
 from transmil_deepgraft_amd import engine as E               # noqa: E402
 from transmil_deepgraft_amd._lib import BF16, F32            # noqa: E402
+sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
+from microbench import GEMM_SEL  # noqa: E402  (the diagnostic build's named selectors)
 
 L = _lib.lib()
 dev = "cuda"
@@ -62,11 +64,11 @@ cases = {
 only = sys.argv[1:] or list(cases)
 for name in only:
     fn, M, Ncol = cases[name]
-    L.tm_debug_set_variant(2, 8)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["stamp_ring"])
     for _ in range(4):
         fn()
     torch.cuda.synchronize()
-    L.tm_debug_set_variant(2, 0)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["auto"])
     nb = ((M + 127) // 128) * ((Ncol + 127) // 128)
     buf = (ctypes.c_ulonglong * (nb * 8))()
     assert L.tm_debug_gemm_stamps(buf, nb * 8) == 0

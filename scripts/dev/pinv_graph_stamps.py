@@ -83,9 +83,6 @@ def analyse(buf, wgs, title, ratio=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--nbh", type=int, default=8)
-    ap.add_argument("--ab", default="", help="comma list of diagnostic split variants to A/B by graph replay "
-                                             "(e.g. 0,6: 6 = write-through epilogue stores)")
-    ap.add_argument("--variant", type=int, default=0, help="split variant of the stamped run")
     args = ap.parse_args()
     dev, nbh = "cuda", args.nbh
     st = E._stream
@@ -111,32 +108,6 @@ def main():
     fwd()
     bwd()
     torch.cuda.synchronize()
-    if args.ab:
-        vs = [int(v) for v in args.ab.split(",")]
-        graphs = {}
-        for v in vs:
-            L.tm_debug_set_split_variant(v)
-            for nm, fn in (("fwd", fwd), ("bwd", bwd)):
-                fn()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    fn()
-                graphs[v, nm] = g
-        L.tm_debug_set_split_variant(0)
-        res = {k: [] for k in graphs}
-        for rnd in range(7):          # interleaved rounds, 20 replays each
-            for k, g in graphs.items():
-                s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                s.record()
-                for _ in range(20):
-                    g.replay()
-                e.record()
-                torch.cuda.synchronize()
-                res[k].append(s.elapsed_time(e) * 1e3 / 20)
-        for k, xs in res.items():
-            print(f"A/B variant {k[0]} {k[1]}: median {np.median(xs):.2f} us  (min {min(xs):.2f})")
-    L.tm_debug_set_split_variant(args.variant)
     results = {}
     ratio = None
     for name, fn, wgs in (("forward chain (tm_pinv_fwd_split)", fwd, fwd_wgs(nbh)),

@@ -1,5 +1,5 @@
 """Per-workgroup phase stamps of the big-tile to_qkv GEMM (256 x 256 tiles, head-major scatter
-epilogue; diagnostic build, variant 12) at the bench shape (M = 8448, N = 1536, K = 512).
+epilogue; diagnostic build, GEMM_SEL stamp_big) at the bench shape (M = 8448, N = 1536, K = 512).
 
     TRANSMIL_HIP_LIB=transmil_deepgraft_amd/libtransmil_hip_diag.so python scripts/dev/qkv_big_stamps.py"""
 import ctypes
@@ -14,7 +14,7 @@ from transmil_deepgraft_amd import _lib                      # noqa: E402
 from transmil_deepgraft_amd import engine as E               # noqa: E402
 from transmil_deepgraft_amd._lib import BF16                 # noqa: E402
 sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
-from microbench import timeit                                 # noqa: E402
+from microbench import GEMM_SEL, timeit                                 # noqa: E402
 
 L = _lib.lib()
 n, dev = 8448, "cuda"
@@ -24,11 +24,11 @@ W = (torch.randn(1536, 512, device=dev) * 0.05).to(torch.bfloat16)
 out = torch.empty(3, 8, n, 64, device=dev, dtype=torch.bfloat16)
 fn = lambda: E.gemm(A, W, out, n, 1536, 512, lda=512, ldb=512, ldc=0, dtype=BF16, qkv=(1, 8, 64, n, 0.125))
 print(f"big-tile QKV (product pick): {timeit(fn, 30):.2f} us per call (graph replay)", flush=True)
-L.tm_debug_set_variant(2, 12)
+L.tm_debug_set_gemm_sel(GEMM_SEL["stamp_big"])
 for _ in range(4):
     fn()
 torch.cuda.synchronize()
-L.tm_debug_set_variant(2, 0)
+L.tm_debug_set_gemm_sel(GEMM_SEL["auto"])
 nb = 6 * 33
 buf = (ctypes.c_ulonglong * (nb * 8))()
 assert L.tm_debug_gemm_stamps(buf, nb * 8) == 0

@@ -1,4 +1,4 @@
-"""Phase stamps of tm_stem_conv_pool (diagnostic build, variant 1): per workgroup of the first 4096,
+"""Phase stamps of tm_stem_conv_pool (diagnostic build, tm_debug_set_stem_stamps): per workgroup of the first 4096,
 shader-clock cycles from start to staged / k loop done / conv tile stored / pool stores issued,
 and the realtime (100 MHz) span -> how many workgroups overlap per CU.
 
@@ -23,10 +23,10 @@ b = (torch.randn(64, device="cuda") * 0.1).to(torch.bfloat16)
 wp = E._pack_stem(w)
 for _ in range(3):
     E._stem_conv_pool(x, wp, b)
-L.tm_debug_set_stem_variant(1)
+L.tm_debug_set_stem_stamps(1)
 E._stem_conv_pool(x, wp, b)
 torch.cuda.synchronize()
-L.tm_debug_set_stem_variant(0)
+L.tm_debug_set_stem_stamps(0)
 buf = (C.c_ulonglong * (4096 * 8))()
 assert L.tm_debug_stem_stamps(buf, 4096 * 8) == 0
 a = np.frombuffer(buf, dtype=np.uint64).reshape(4096, 8).astype(np.int64)

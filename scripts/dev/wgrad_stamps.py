@@ -1,4 +1,4 @@
-"""Per-workgroup phases of the split-K weight-gradient ring GEMM (diagnostic build, gemm variant 8
+"""Per-workgroup phases of the split-K weight-gradient ring GEMM (diagnostic build, GEMM_SEL stamp_ring
 stamps) at the step's shapes: dWo / dW_fc1 (512 x 512, K = 8448 / 8192) and dWqkv (1536 x 512,
 K = 8448); also the same products with the operands stored k-contiguous (A = dY^T, B = X^T
 materialised), to separate the k-row (a_trans / b_kn) image fill from the k-contiguous one.
@@ -16,6 +16,8 @@ sys.path.insert(0, os.getcwd())
 from transmil_deepgraft_amd import _lib                      # noqa: E402
 from transmil_deepgraft_amd import engine as E               # noqa: E402
 from transmil_deepgraft_amd._lib import BF16, F32            # noqa: E402
+sys.path.insert(0, os.path.join(os.getcwd(), "scripts"))
+from microbench import GEMM_SEL  # noqa: E402  (the diagnostic build's named selectors)
 
 L = _lib.lib()
 dev = "cuda"
@@ -23,11 +25,11 @@ torch.manual_seed(0)
 
 
 def run(name, fn, nb):
-    L.tm_debug_set_variant(2, 8)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["stamp_ring"])
     for _ in range(4):
         fn()
     torch.cuda.synchronize()
-    L.tm_debug_set_variant(2, 0)
+    L.tm_debug_set_gemm_sel(GEMM_SEL["auto"])
     buf = (ctypes.c_ulonglong * (nb * 8))()
     assert L.tm_debug_gemm_stamps(buf, nb * 8) == 0
     st = np.frombuffer(buf, dtype=np.uint64).reshape(nb, 8).astype(np.int64)

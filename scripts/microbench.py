@@ -3,9 +3,9 @@
     python scripts/microbench.py [--n 8192] [--reps 50]
 
 Each case is run `reps` times between two events on the current stream; the
-median of 5 rounds is printed.  Used to A/B kernel variants on the GPU box: it runs on the
-diagnostic build (`make -C transmil_deepgraft_amd/csrc diag`), whose tm_debug_* switches select
-the variants; the product library has none.
+median of 5 rounds is printed.  It runs on the diagnostic build (`make -C transmil_deepgraft_amd/csrc
+diag`), whose tm_debug_* selectors force a path between shipped kernels or pick a stamped
+instantiation; the product library has none.
 """
 import argparse
 import ctypes as C
@@ -23,6 +23,20 @@ os.environ.setdefault("TRANSMIL_HIP_LIB", os.path.join(ROOT, "transmil_deepgraft
 from transmil_deepgraft_amd import _lib  # noqa: E402
 from transmil_deepgraft_amd import engine as E  # noqa: E402
 from transmil_deepgraft_amd._lib import BF16, F32  # noqa: E402
+
+# the diagnostic build's selectors: enum GemmSel (csrc/gemm.hip), enum NysSel (csrc/nystrom.hip)
+GEMM_SEL = {"auto": 0, "force_reg": 1, "force_ring": 2, "force_ring160": 3, "force_big": 4,
+            "stamp_ring": 5, "stamp_big": 6}
+NYS_SEL = {"auto": 0, "stamp_a1_fwd": 1, "stamp_a3_fwd": 2, "stamp_a1_bwd": 3, "stamp_a1_bwd_chunk": 4,
+           "stamp_a3_bwd": 5, "stamp_a3_bwd_chunk": 6}
+
+
+def set_gemm_sel(name):
+    _lib.lib().tm_debug_set_gemm_sel(GEMM_SEL[name])
+
+
+def set_nys_sel(name):
+    _lib.lib().tm_debug_set_nys_sel(NYS_SEL[name])
 
 
 def timeit(fn, reps, graph=True):
@@ -65,7 +79,7 @@ def main():
     ap.add_argument("--only", default="")
     ap.add_argument("--eager", action="store_true")
     ap.add_argument("--stamps", action="store_true", help="a1_fwd in-kernel s_memtime stamps")
-    ap.add_argument("--gemm-ab", action="store_true", help="also time the GEMMs on the register-staged loop")
+    ap.add_argument("--gemm-ab", action="store_true", help="also time the GEMMs with each path forced (GEMM_SEL force_*)")
     ap.add_argument("--split-stamps", action="store_true", help="per-wave s_memtime stamps of the split pinv chain")
     args = ap.parse_args()
     dev = "cuda"
@@ -143,16 +157,13 @@ def main():
     sout = torch.empty(nbh, 256, 256, device=dev)
     sdz = torch.empty(2 * nbh * 65536, dtype=torch.bfloat16, device=dev)
     _lib.call("tm_split_f32", E._p(pdz), E._p(sdz), nbh * 65536, st())
-    for v, nm in ((0, "per-level launches"), (8, "persistent team"), (9, "team, plain DMA (probe)")):
-        _lib.lib().tm_debug_set_split_variant(v)
-        case(f"pinv_fwd split [{nm}]", lambda: _lib.call("tm_pinv_fwd_split", E._p(X), E._p(Xs), nbh, 6,
-                                                           E._p(ssaved), st()), 24 * f)
+    case("pinv_fwd split", lambda: _lib.call("tm_pinv_fwd_split", E._p(X), E._p(Xs), nbh, 6, E._p(ssaved), st()),
+         24 * f)
 
-        def bwd():
-            swork[:2 * nbh * 65536 // 2].view(torch.bfloat16).copy_(sdz)
-            _lib.call("tm_pinv_bwd_split", E._p(X), E._p(Xs), nbh, 6, E._p(ssaved), E._p(swork), 1, E._p(sout), st())
-        case(f"pinv_bwd split [{nm}]", bwd, 48 * f)
-    _lib.lib().tm_debug_set_split_variant(0)
+    def bwd():
+        swork[:2 * nbh * 65536 // 2].view(torch.bfloat16).copy_(sdz)
+        _lib.call("tm_pinv_bwd_split", E._p(X), E._p(Xs), nbh, 6, E._p(ssaved), E._p(swork), 1, E._p(sout), st())
+    case("pinv_bwd split", bwd, 48 * f)
     if args.split_stamps:
         import numpy as np
         # workgroups per launch: L1 (S + abs sums), A_0, B_0, (A_k, B_k) k=1..4, A_5, B_5, F
@@ -188,9 +199,9 @@ def main():
     _lib.call("tm_split_f32", E._p(pdz), E._p(swork), nbh * 65536, st())
     case("pinv_bwd split (+softmax bwd)", lambda: _lib.call("tm_pinv_bwd_split", E._p(X), E._p(Xs), nbh, 6,
                                                             E._p(ssaved), E._p(swork), 1, E._p(sout), st()), 32 * f)
-    for gv in ((0, 1, 2, 4, 7) if args.gemm_ab else (0,)):
-        _lib.lib().tm_debug_set_variant(2, gv)
-        tag[0] = {0: "", 1: "[2 LDS buf] ", 2: "[4-stage ring] ", 4: "[persistent ring] ", 7: "[big tile] "}[gv]
+    for gs in (("auto", "force_reg", "force_ring", "force_ring160", "force_big") if args.gemm_ab else ("auto",)):
+        set_gemm_sel(gs)
+        tag[0] = "" if gs == "auto" else f"[{gs}] "
         # ---------------- GEMMs ----------------
         pool = E.Pool(dev)
         xn = torch.randn(n, 512, device=dev).to(bf)
@@ -240,7 +251,7 @@ def main():
     case("torch copy 52 MB fp32", lambda: slabq.view(-1).copy_(nf), byts=2 * n * 1536 * 4)
     case("splitk_reduce 33 x 512", lambda: _lib.call("tm_splitk_reduce", E._p(slab2), E._p(ob), 33, 512,
                                                          C.c_float(1.0), 0, None, st()))
-    _lib.lib().tm_debug_set_variant(2, 0)
+    set_gemm_sel("auto")
     tag[0] = ""
 
     # ---------------- NystromAttention core ----------------
@@ -265,13 +276,8 @@ def main():
     case("a1_fwd", lambda: _lib.call("tm_nys_a1_fwd", BF16, E._p(q), E._p(v), E._p(kl_t), E._p(y_t), E._p(wconv),
                                      nbh, 8, n, E._p(merged), E._p(lse1), st()),
          4 * nbh * n * 256 * 64, 3 * n * 512 * 2)
-    for var, nm in ((11, "no conv"), (12, "no attention"), (13, "prologue only"),
-                    (14, "legacy 128-query kernel")):
-        _lib.lib().tm_debug_set_variant(1, var)
-        case(f"a1_fwd [{nm}]", lambda: _lib.call("tm_nys_a1_fwd", BF16, E._p(q), E._p(v), E._p(kl_t), E._p(y_t),
-                                                E._p(wconv), nbh, 8, n, E._p(merged), E._p(lse1), st()))
     if args.stamps:
-        _lib.lib().tm_debug_set_variant(1, 19)
+        set_nys_sel("stamp_a1_fwd")
         _lib.call("tm_nys_a1_fwd", BF16, E._p(q), E._p(v), E._p(kl_t), E._p(y_t), E._p(wconv), nbh, 8, n,
                   E._p(merged), E._p(lse1), st())
         torch.cuda.synchronize()
@@ -291,7 +297,7 @@ def main():
         d = a[:, :, 6] - a[:, :, 0]
         print(f"  wave lifetime median {int(np.median(d))} max {int(d.max())}; "
               f"last end - first start {int(a[:, :, 6].max() - t0)}")
-    _lib.lib().tm_debug_set_variant(1, 0)
+    set_nys_sel("auto")
     dmerged = torch.randn(1, n, 512, device=dev).to(bf)
     dv = torch.empty(nbh, n, 64, device=dev)
     d1 = torch.empty(nbh, n, device=dev)

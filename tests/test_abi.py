@@ -214,3 +214,23 @@ def test_only_the_documented_entry_point_synchronises():
     # ... and that one wait sits in the tuning branch, which refuses a capturing stream
     assert src.index("hipEventSynchronize") > src.index("if (tune && !p->tuned)")
     assert "not during stream capture" in src
+
+
+def test_product_sources_read_no_environment():
+    """No product source reads the environment (TM_DIAG-only code excluded): a kernel pick that
+    follows an environment variable is an unvalidated configuration of the product."""
+    import glob
+    hits = [os.path.basename(path)
+            for path in sorted(glob.glob(os.path.join(ROOT, "transmil_deepgraft_amd", "csrc", "*.hip")) +
+                               glob.glob(os.path.join(ROOT, "transmil_deepgraft_amd", "csrc", "*.h")))
+            if "getenv" in _strip_diag_blocks(open(path).read())]
+    assert not hits, hits
+
+
+def test_engine_reads_no_tm_environment_variable():
+    """engine.py takes no TM_* switch from the environment (its rounding-relevant choices -- the
+    weight-gradient splits, the LayerNorm backward's rows per block, the class-row q products --
+    are constants of the code)."""
+    src = open(os.path.join(ROOT, "transmil_deepgraft_amd", "engine.py")).read()
+    assert not re.search(r"environ|getenv", src), "engine.py reads the environment"
+    assert not re.search(r"[\"']TM_[A-Z0-9_]+[\"']", src), "engine.py names a TM_* variable"

@@ -87,7 +87,6 @@ _SIGS = {
     "tm_nys_a3_fwd": (I, [I, P, P, P, I, I, P, P, P, P]),
     "tm_nys_a3_fwd_sim2": (I, [P, P, P, P, I, I, P, P, P, P]),
     "tm_nys_a1_fwd": (I, [I, P, P, P, P, P, I, I, I, P, P, P]),
-    "tm_nys_rowdot_cast": (I, [I, P, P, I, P, P, P]),
     "tm_cast_f32": (I, [I, P, P, L, P]),
     "tm_nys_conv_bwd_workspace": (L, [I, I, I]),
     "tm_nys_conv_bwd": (I, [I, P, P, P, P, I, I, I, P, P, P, P, P, P]),
@@ -98,7 +97,6 @@ _SIGS = {
     "tm_nys_a3_bwd": (I, [I, P, P, P, P, P, P, I, I, I, P, P, P, P, I, P, P]),
     "tm_nys_assemble_dqkv": (I, [I, P, P, P, P, P, I, I, I, Fl, P, P]),
     "tm_nys_a3_bwd_fused": (I, [P, P, P, P, P, P, I, I, I, P, I, I, P, P, P, P, P, P]),
-    "tm_nys_assemble_q": (I, [I, P, I, P, P, I, I, I, Fl, P, P]),
     "tm_nys_a3_bwd_slabs": (I, [I, I]),
     "tm_nys_assemble_q_slab": (I, [I, P, I, P, P, I, I, I, I, Fl, P, P]),
     "tm_nys_assemble_q_slab_inplace": (I, [P, P, I, I, I, I, Fl, P, P]),
@@ -165,12 +163,12 @@ _SIGS = {
 EXPORTED = tuple(_SIGS)
 
 # Entry points of the diagnostic build only (`make -C transmil_deepgraft_amd/csrc diag` ->
-# libtransmil_hip_diag.so, selected with TRANSMIL_HIP_LIB; scripts/microbench.py): kernel-variant
-# switches and timing stamps.  Not part of the ABI; the product library does not export them.
+# libtransmil_hip_diag.so, selected with TRANSMIL_HIP_LIB; scripts/microbench.py): named selectors
+# (forced paths between shipped kernels, stamped instantiations) and the timing stamps.  Not part of the ABI; the product library does not export them.
 DIAG_SIGS = {
-    "tm_debug_set_variant": (None, [I, I]),
+    "tm_debug_set_gemm_sel": (None, [I]),
+    "tm_debug_set_nys_sel": (None, [I]),
     "tm_debug_xcc_map": (I, [P, I, I, P]),
-    "tm_debug_set_split_variant": (None, [I]),
     "tm_debug_set_split_stamps": (None, [P]),
     "tm_debug_a1_stamps": (I, [P, I]),
     "tm_debug_gemm_stamps": (I, [P, I]),

@@ -27,10 +27,12 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 #define TM_DEV __device__ __forceinline__
 
-// Ablation / diagnostic switches exist only in the TM_DIAG build (`make diag` ->
-// libtransmil_hip_diag.so, loaded by scripts/microbench.py through TRANSMIL_HIP_LIB).  The product
-// library has no process-global mutable state: every selector is the constant 0 (the default
-// kernel), the alternative kernels are not compiled and no tm_debug_* symbol is exported.
+// Diagnostic selectors exist only in the TM_DIAG build (`make diag` -> libtransmil_hip_diag.so,
+// loaded by scripts/microbench.py through TRANSMIL_HIP_LIB).  They are named (GemmSel in gemm.hip,
+// NysSel in nystrom.hip) and of two kinds only: the timing-stamp instantiation of a shipped kernel,
+// or a forced path between shipped kernels.  The product library has no process-global mutable
+// state: every selector is the constant 0 (the product's own pick), the stamped instantiations
+// are not compiled and no tm_debug_* symbol is exported.
 #ifdef TM_DIAG
 #define TM_DIAG_VAR(v) (v)
 #else

@@ -25,7 +25,7 @@
 
 #include "common.h"
 
-#include <cstdlib>
+#include <type_traits>
 #include "../../include/transmil_hip.h"
 
 namespace {
@@ -200,7 +200,7 @@ TM_DEV void gemm_epilogue(const f32x16 (&acc)[2][2], char* smem, OutT* __restric
 // (image rows of TBN + 8 floats), all in the same 8 columns (NT is a multiple of TBN / 8).
 // Rolled loops (`unroll 1`): the epilogue runs once per tile, so its code runs from a cold
 // instruction cache -- unrolled over IT chunks and every mode it was ~5k instructions and took
-// ~8k cycles of a 128 x 128 tile, against ~1.3k for the bare stores (scripts/dev/gemm_epi_probe.py).
+// ~8k cycles of a 128 x 128 tile, against ~1.3k for the bare stores.
 // The addend loads (residual / accumulate source) of chunk it + 1 go out before chunk it's
 // stores: gfx9 counts stores on vmcnt, so a load issued after a store waits for its write-back.
 template <typename OutT, int TBN, int ROWS, int NT, int KIND>
@@ -432,17 +432,18 @@ TM_DEV void tile_split_of_block(int& m0, int& n0, int& z) {
   n0 = (rr % ntx) * BN;
 }
 
-// NBUF = 2: double-buffered LDS (one barrier per k-tile); NBUF = 1: one LDS buffer, two
-// barriers per k-tile, half the LDS -> twice the resident workgroups per CU.
-template <typename T, typename OutT, bool A_T, bool B_KN, int NBUF = 2>
+// Register-staged loop: the next k-tile's global loads are in flight in registers while the
+// current one multiplies; one LDS buffer, two barriers per k-tile (a second LDS buffer saved a
+// barrier but halved the resident workgroups per CU, and was slower).
+template <typename T, typename OutT, bool A_T, bool B_KN>
 __global__ __launch_bounds__(256) void gemm_kernel(const T* __restrict__ A, const T* __restrict__ B,
                                                    OutT* __restrict__ C, tm_gemm_args g) {
   using TT = Tile<T>;
   constexpr int BK = TT::BK;
-  constexpr int AE = tile_elems<T, A_T>(), BE = tile_elems<T, B_KN>();
+  constexpr int AE = tile_elems<T, A_T>();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   T* As0 = (T*)smem;
-  T* Bs0 = As0 + NBUF * AE;
+  T* Bs0 = As0 + AE;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
@@ -473,29 +474,18 @@ __global__ __launch_bounds__(256) void gemm_kernel(const T* __restrict__ A, cons
       else load_rows(sb, B, g.ldb, n0, g.N, k0, kend, tid);
     }
   };
-  auto lstore = [&](int buf) {
-    if constexpr (A_T) store_cols(As0 + buf * AE, sa, tid); else store_rows(As0 + buf * AE, sa, tid);
-    if constexpr (B_KN) store_cols(Bs0 + buf * BE, sb, tid); else store_rows(Bs0 + buf * BE, sb, tid);
+  auto lstore = [&]() {
+    if constexpr (A_T) store_cols(As0, sa, tid); else store_rows(As0, sa, tid);
+    if constexpr (B_KN) store_cols(Bs0, sb, tid); else store_rows(Bs0, sb, tid);
   };
 
-  if constexpr (NBUF == 1) {
-    if (nk > 0) gload(kbeg);
-  } else {
-    if (nk > 0) {
-      gload(kbeg);
-      lstore(0);
-    }
-    __syncthreads();
-  }
+  if (nk > 0) gload(kbeg);
   for (int kt = 0; kt < nk; ++kt) {
-    const int cur = NBUF == 1 ? 0 : (kt & 1);
-    if constexpr (NBUF == 1) {
-      lstore(0);
-      __syncthreads();
-    }
+    lstore();
+    __syncthreads();
     if (kt + 1 < nk) gload(kbeg + (kt + 1) * BK);
-    const T* as = As0 + cur * AE;
-    const T* bs = Bs0 + cur * BE;
+    const T* as = As0;
+    const T* bs = Bs0;
 #pragma unroll
     for (int s = 0; s < TT::KSTEPS; ++s) {
       vec8<T> af[2], bfr[2];
@@ -508,7 +498,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(const T* __restrict__ A, cons
 #pragma unroll
         for (int j = 0; j < 2; ++j) mma16(acc[i][j], af[i], bfr[j]);
     }
-    if (NBUF == 2 && kt + 1 < nk) lstore(cur ^ 1);
     __syncthreads();
   }
 
@@ -516,20 +505,20 @@ __global__ __launch_bounds__(256) void gemm_kernel(const T* __restrict__ A, cons
 }
 
 // ---------------------------------------------------------------------------
-// bf16 main loop v2: a 4-stage ring of LDS tiles filled by global_load_lds (16 B per
-// lane, no VGPR round trip), so three 64-deep k-tiles are in flight while one is
-// multiplied.  Per stage: A and B 128 x 64 bf16 images of 16 KB each (128 KB ring,
-// one workgroup per CU).  Sync per k-tile: counted `s_waitcnt vmcnt` (never 0 in
-// steady state) + raw s_barrier, which also retires the buffer the next prefetch
-// overwrites (read in the previous iteration).
+// bf16 main loop v2: a 2-stage ring of LDS tiles filled by global_load_lds (16 B per
+// lane, no VGPR round trip), so the next 64-deep k-tile is in flight while one is
+// multiplied.  Per stage: A and B 128 x 64 bf16 images of 16 KB each (64 KB ring; 69.6 KB
+// with the epilogue image, two workgroups per CU).  Sync per k-tile: `s_waitcnt vmcnt(0)`
+// + raw s_barrier, which also retires the buffer the next prefetch overwrites (read in the
+// previous iteration).
 // LDS images (bank-clean reads, swizzle applied on the global source address):
 //   k-contiguous operand [128 rows][64 k]: 16-B chunk c of row r at slot c ^ ((r >> 1) & 7)
 //     -> fragment = one ds_read_b128 per lane (16 consecutive rows hit 16 distinct bank groups)
 //   k-strided operand [64 k][128 rows]: chunk c of k-row k at slot c ^ (2 * (k & 3))
 //     -> fragment = two ds_read_b64_tr_b16 (4 k-rows x 2 chunks per 16-lane group all distinct)
-constexpr int NSTAGE = 4;
+constexpr int NSTAGE = 2;
 constexpr int STAGE_BYTES = 2 * 128 * 64 * 2;  // A + B images
-[[maybe_unused]] constexpr int RING_BYTES = NSTAGE * STAGE_BYTES;
+constexpr int RING_BYTES = NSTAGE * STAGE_BYTES;
 
 // One operand image of one stage: 16 wave-instructions of 1 KB, 2 per wave (8 waves).
 template <bool KSTRIDED>
@@ -626,15 +615,11 @@ TM_DEV void rd_frag(bf16x8& f, unsigned base, const unsigned (&kc)[4]) {
 
 // one 64-deep k-tile of one wave's 32 x 64 subtile: 4 k-steps of 2 MFMAs, the LDS reads of
 // step s+1 in flight while step s multiplies
-// SWAP: the products are issued as (B, A) -- acc[j] holds the TRANSPOSED 32 x 32 tile (lane l:
-// output row l & 31, 16 output columns per lane), the register layout gemm_pr_kernel stores from
-template <bool A_KS, bool B_KS, bool SWAP = false>
+template <bool A_KS, bool B_KS>
 TM_DEV void ring_tile_mma(f32x16 (&acc)[2], unsigned abase, unsigned b0, unsigned b1, const unsigned (&akc)[4],
                           const unsigned (&bkc0)[4], const unsigned (&bkc1)[4]) {
   constexpr int RS = (A_KS ? 2 : 1) + 2 * (B_KS ? 2 : 1);   // LDS reads per k-step
-  auto mm = [](f32x16& c, const bf16x8& a, const bf16x8& b) {
-    if constexpr (SWAP) mma16(c, b, a); else mma16(c, a, b);
-  };
+  auto mm = [](f32x16& c, const bf16x8& a, const bf16x8& b) { mma16(c, a, b); };
   bf16x8 a[2], b[2][2];
   rd_frag<A_KS, 0>(a[0], abase, akc); rd_frag<B_KS, 0>(b[0][0], b0, bkc0); rd_frag<B_KS, 0>(b[0][1], b1, bkc1);
   rd_frag<A_KS, 1>(a[1], abase, akc); rd_frag<B_KS, 1>(b[1][0], b0, bkc0); rd_frag<B_KS, 1>(b[1][1], b1, bkc1);
@@ -654,7 +639,7 @@ TM_DEV void ring_tile_mma(f32x16 (&acc)[2], unsigned abase, unsigned b0, unsigne
   mm(acc[1], a[1], b[1][1]);
 }
 
-// diagnostics (variant 8 only): per-workgroup shader-clock stamps of the ring kernel, read by
+// diagnostics (the STAMP instantiations only): per-workgroup shader-clock stamps of the ring kernel, read by
 // tm_debug_gemm_stamps: [block][8] = realtime start, t start, first tile landed, k-loop done,
 // accumulators staged, epilogue stores issued, stores retired, realtime end
 __device__ unsigned long long g_gemm_stamps[2048 * 8];
@@ -670,7 +655,7 @@ TM_DEV void ring_stamp(unsigned long long (&ts)[8], int slot, bool real = false)
   }
 }
 
-template <typename OutT, bool A_T, bool B_KN, int NS = NSTAGE, bool STAMP = false, int KIND = EK_ANY>
+template <typename OutT, bool A_T, bool B_KN, bool STAMP = false, int KIND = EK_ANY>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void gemm_ring_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                         OutT* __restrict__ C, tm_gemm_args g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -709,31 +694,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void g
   const unsigned ring = lds_u32(smem);
 
   auto issue = [&](int kt) {
-    char* st = smem + (kt % NS) * STAGE_BYTES;
+    char* st = smem + (kt % NSTAGE) * STAGE_BYTES;
     const int k0 = kbeg + kt * 64;
     glds_tile<A_T>(st, A, g.lda, m0, g.M, k0, wave, lane);
     glds_tile<B_KN>(st + STAGE_BYTES / 2, B, g.ldb, n0, g.N, k0, wave, lane);
   };
 #pragma unroll
-  for (int t = 0; t < NS - 1; ++t)
+  for (int t = 0; t < NSTAGE - 1; ++t)
     if (t < nk) issue(t);
 
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's pieces of tile kt have landed once at most (tiles issued after kt) x 4 loads remain
-    const int ahead = min(NS - 2, nk - 1 - kt);
+    // (NSTAGE = 2: tile kt + 1 is not yet issued, so this waits for all)
+    const int ahead = min(NSTAGE - 2, nk - 1 - kt);
     if (ahead >= 2) wait_vm<8>(); else if (ahead == 1) wait_vm<4>(); else wait_vm<0>();
     __builtin_amdgcn_s_barrier();  // every wave's pieces landed; every wave done reading tile kt-1
     asm volatile("" ::: "memory");
     if (STAMP && kt == 0) ring_stamp<STAMP>(ts, 2);
-    if (kt + NS - 1 < nk) issue(kt + NS - 1);  // overwrites tile kt-1's buffer
-    const unsigned sb = ring + (kt % NS) * STAGE_BYTES;
+    if (kt + NSTAGE - 1 < nk) issue(kt + NSTAGE - 1);  // overwrites tile kt-1's buffer
+    const unsigned sb = ring + (kt % NSTAGE) * STAGE_BYTES;
     ring_tile_mma<A_T, B_KN>(acc, (A_T ? aks : 0) + sb, (B_KN ? bks0 : 0) + sb, (B_KN ? bks1 : 0) + sb,
                              akc, bkc0, bkc1);
     if constexpr (COLSUM) {
       // the bias gradient of the same dY: this tile's 64 k-rows of A summed per column (thread:
       // 16-B column chunk cs_c of k-rows cs_r and cs_r + 32), behind the tile's MFMAs
       if (do_cs) {
-        const char* img = smem + (kt % NS) * STAGE_BYTES;
+        const char* img = smem + (kt % NSTAGE) * STAGE_BYTES;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           const int kk = cs_r + 32 * j;
@@ -751,25 +737,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void g
   for (int j = 0; j < 2; ++j) stage_acc(ep, acc[j], wm * 32, wn * 64 + j * 32, lane);
   __syncthreads();
   ring_stamp<STAMP>(ts, 4);
-  if (STAMP && g.drop_scale < 0.f) {
-    // diagnostics: image reads only, no global stores (drop_scale -1) or plain bf16/f32 stores of
-    // the image with no other epilogue work (drop_scale -2)
-    const float* ep2 = (const float*)smem;
-    for (int c = tid; c < BM * 16; c += 512) {
-      const int lr = c / 16, lc = (c % 16) * 8;
-      const f32x4 lo = *(const f32x4*)(ep2 + lr * EP_ROW + lc), hi = *(const f32x4*)(ep2 + lr * EP_ROW + lc + 4);
-      if (g.drop_scale < -1.5f) {
-        OutT* dst = C + (size_t)(m0 + lr) * g.ldc + n0 + lc;
-        if (m0 + lr < g.M) {
-          vec8<OutT> o;
-          for (int e = 0; e < 4; ++e) { o[e] = from_f<OutT>(lo[e]); o[e + 4] = from_f<OutT>(hi[e]); }
-          store8<OutT>(dst, o);
-        }
-      } else {
-        asm volatile("" ::"v"(lo), "v"(hi));
-      }
-    }
-  } else
   gemm_epilogue_rows<OutT, BN, BM, 512, KIND>(smem, C, g, m0, n0, zs);
   if constexpr (COLSUM) {
     if (do_cs) {
@@ -904,315 +871,6 @@ __global__ __launch_bounds__(640) void gemm_ring160_kernel(const bf16* __restric
 }
 
 // ---------------------------------------------------------------------------
-// Persistent bf16 GEMM: one 512-thread workgroup per CU walks its tiles (t = blockIdx.x +
-// i * gridDim.x, XCD-clustered) as ONE stream of 64-deep k-steps, so the global_load_lds ring
-// keeps prefetching across tile boundaries: the next tile's first k-tiles are in flight while
-// the current tile's epilogue runs (from its own LDS region).  Ring: 3 stages x 32 KB; epilogue
-// image 64 rows x EP_ROW fp32 (two halves per tile).  Same fragment reads and epilogue as the
-// ring kernel above; the split-K index rides in the tile id.
-constexpr int PSTAGE = 3;
-[[maybe_unused]] constexpr int PERSIST_LDS = PSTAGE * STAGE_BYTES + 64 * EP_ROW * 4;
-
-struct PTile {
-  int i, t, m0, n0, split, kbeg, nk, kt;
-};
-
-TM_DEV void ptile_set(PTile& c, int ntiles, int tiles_m, int tiles_n, const tm_gemm_args& g) {
-  c.t = blockIdx.x + c.i * gridDim.x;
-  c.kt = 0;
-  if (c.t >= ntiles) { c.nk = 0; return; }
-  // XCD clustering: workgroup b runs on XCD b % 8 and owns tiles t = b (mod gridDim.x); renumber
-  // so each XCD's tiles form contiguous row-major runs (shared A panels stay in its L2)
-  const int per = tiles_m * tiles_n;
-  const int x = c.t % 8, q = ntiles / 8, r = ntiles % 8;
-  const int id = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + c.t / 8;
-  c.split = id / per;
-  const int rr = id % per;
-  c.m0 = (rr / tiles_n) * BM;
-  c.n0 = (rr % tiles_n) * BN;
-  c.kbeg = c.split * g.k_per_split;
-  c.nk = (min(g.K, c.kbeg + g.k_per_split) - c.kbeg) / 64;
-}
-
-template <typename OutT, bool A_T, bool B_KN>
-__global__ __launch_bounds__(512) void gemm_persist_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
-                                                           OutT* __restrict__ C, tm_gemm_args g, int tiles_m,
-                                                           int tiles_n) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  char* epi = smem + PSTAGE * STAGE_BYTES;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int ntiles = tiles_m * tiles_n * g.splits;
-
-  unsigned akc[4] = {0, 0, 0, 0}, bkc0[4] = {0, 0, 0, 0}, bkc1[4] = {0, 0, 0, 0};
-  unsigned aks = 0, bks0 = 0, bks1 = 0;
-  if constexpr (A_T) aks = ks_addr(wm * 32, lane); else kc_addrs(akc, wm * 32, lane);
-  if constexpr (B_KN) {
-    bks0 = ks_addr(wn * 64, lane) + STAGE_BYTES / 2;
-    bks1 = ks_addr(wn * 64 + 32, lane) + STAGE_BYTES / 2;
-  } else {
-    kc_addrs(bkc0, wn * 64, lane);
-    kc_addrs(bkc1, wn * 64 + 32, lane);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { bkc0[s] += STAGE_BYTES / 2; bkc1[s] += STAGE_BYTES / 2; }
-  }
-  const unsigned ring = lds_u32(smem);
-
-  PTile is{}, cs{};
-  is.i = 0;
-  ptile_set(is, ntiles, tiles_m, tiles_n, g);
-  while (is.nk == 0 && is.t < ntiles) { ++is.i; ptile_set(is, ntiles, tiles_m, tiles_n, g); }  // empty splits
-  cs = is;
-  int issued = 0, done = 0;
-  auto issue = [&]() {
-    char* st = smem + (issued % PSTAGE) * STAGE_BYTES;
-    const int k0 = is.kbeg + is.kt * 64;
-    glds_tile<A_T>(st, A, g.lda, is.m0, g.M, k0, wave, lane);
-    glds_tile<B_KN>(st + STAGE_BYTES / 2, B, g.ldb, is.n0, g.N, k0, wave, lane);
-    ++issued;
-    if (++is.kt == is.nk) {
-      do { ++is.i; ptile_set(is, ntiles, tiles_m, tiles_n, g); } while (is.nk == 0 && is.t < ntiles);
-    }
-  };
-#pragma unroll
-  for (int p = 0; p < PSTAGE - 1; ++p)
-    if (is.t < ntiles) issue();
-
-  f32x16 acc[2];
-  acc[0] = (f32x16){};
-  acc[1] = (f32x16){};
-  while (cs.t < ntiles) {
-    // step `done` landed once at most (issued - done - 1) younger steps (4 loads each) remain
-    if (issued - done - 1 >= 1) wait_vm<4>(); else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();  // every wave's pieces landed; every wave done with step done-1
-    asm volatile("" ::: "memory");
-    if (is.t < ntiles) issue();    // overwrites step done-1's slot
-    const unsigned sb = ring + (done % PSTAGE) * STAGE_BYTES;
-    ring_tile_mma<A_T, B_KN>(acc, (A_T ? aks : 0) + sb, (B_KN ? bks0 : 0) + sb, (B_KN ? bks1 : 0) + sb,
-                             akc, bkc0, bkc1);
-    ++done;
-    if (++cs.kt == cs.nk) {
-      // epilogue of this tile from the epilogue image (two 64-row halves); the next tile's
-      // first k-steps are already in flight
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        if ((wm >> 1) == half) {
-#pragma unroll
-          for (int j = 0; j < 2; ++j) stage_acc((float*)epi, acc[j], (wm & 1) * 32, wn * 64 + j * 32, lane);
-        }
-        __syncthreads();
-        gemm_epilogue_rows<OutT, BN, 64, 512>(epi, C, g, cs.m0 + half * 64, cs.n0, cs.split);
-        __syncthreads();
-      }
-      wait_vm<0>();   // the epilogue's own loads / stores (their count is data dependent)
-      acc[0] = (f32x16){};
-      acc[1] = (f32x16){};
-      do { ++cs.i; ptile_set(cs, ntiles, tiles_m, tiles_n, g); } while (cs.nk == 0 && cs.t < ntiles);
-    }
-  }
-}
-
-#ifdef TM_DIAG
-// ---------------------------------------------------------------------------
-// Persistent ring GEMM with the epilogue straight from the accumulator registers (gemm_pr_kernel):
-// two 512-thread workgroups per CU (64 KB of LDS each: the 2-stage LDS-DMA ring and nothing else),
-// each walking its tiles t = blockIdx.x + i * gridDim.x (XCD-clustered, ptile_set) as ONE stream of
-// 64-deep k-steps.  What it removes, per tile, from the ring kernel's timeline (stamps,
-// scripts/dev/gemm_stamps2.py, profiles/r05c_gemm_stamps.txt -- QKV: first tile landed 2.8 k,
-// k-loop 10.6 k, accumulator staging 1.2 k, epilogue 2.6 k cycles per tile):
-//   * the first k-step of the next tile is already in flight while this tile's epilogue runs;
-//   * no LDS epilogue image: the products are issued transposed (ring_tile_mma<.., SWAP>), so each
-//     lane holds 16 output COLUMNS of one output row; one cross-half exchange (lanes l, l ^ 32)
-//     gives every lane 8 consecutive columns -> the epilogue works on 8-column row chunks as the
-//     staged one does (bias, pre-activation, GELU, dropout, residual, row map, QKV scatter) and
-//     stores 16 B (bf16) / 32 B (fp32) per lane with no barrier and no LDS round trip;
-//   * the two workgroups of a CU drift apart after their first tiles, so one's epilogue and first
-//     operand fill overlap the other's MFMA k-loop.
-// Chunk (j, p) of a lane: row m0 + 32 wm + (l & 31), columns n0 + 64 wn + 32 j + 16 p + 8 (l >> 5).
-constexpr int PR_NS = 2;
-[[maybe_unused]] constexpr int PR_LDS = PR_NS * STAGE_BYTES;   // 64 KB
-
-template <typename OutT, int KIND>
-TM_DEV void pr_epilogue_chunk(OutT* __restrict__ C, const tm_gemm_args& g, int m, int n, const float (&v)[8],
-                              uint64_t seed) {
-  const int ne = min(8, g.N - n);
-  if (ne <= 0 || m >= g.M) return;
-  float bv[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (g.bias) {
-    if (ne == 8 && ((uintptr_t)g.bias & 15) == 0) { const f32x8 t8 = load8<float>(g.bias + n); for (int e = 0; e < 8; ++e) bv[e] = t8[e]; }
-    else { for (int e = 0; e < ne; ++e) bv[e] = g.bias[n + e]; }
-  }
-  if constexpr (KIND == EK_QKV) {   // 8 columns never straddle a head (dh % 8 == 0, checked on the host)
-    const int inner = g.nh * g.dh;
-    const int which = n / inner, hh = (n % inner) / g.dh, d = n % g.dh;
-    const float qs = which == 0 ? g.qscale : 1.f;
-    const int bag = m / g.seq, t = m - bag * g.seq;
-    OutT* dst = C + ((((long long)which * g.nbags + bag) * g.nh + hh) * g.seq + t) * g.dh + d;
-    vec8<OutT> o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = from_f<OutT>((v[e] * g.alpha + bv[e]) * qs);
-    store8<OutT>(dst, o);
-    return;
-  } else if constexpr (KIND == EK_PLAIN) {
-    vec8<OutT> o;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) o[e] = from_f<OutT>(v[e] * g.alpha + bv[e]);
-    OutT* dst = C + (size_t)m * g.ldc + n;
-    if (ne == 8 && g.ldc % 8 == 0) store8<OutT>(dst, o);
-    else { for (int e = 0; e < ne; ++e) dst[e] = o[e]; }
-    return;
-  } else {
-    // runtime mode: row map (TransMIL grid duplication / padding skip), pre-activation, GELU,
-    // dropout, residual / accumulate -- the same per-element order as gemm_epilogue_rows
-    int row = m, dup = -1;
-    if (g.grp_in > 0) {
-      const int bag = m / g.grp_in, t = m - bag * g.grp_in - g.skip;
-      if (t < 0) return;
-      if (t < g.dup_n) dup = bag * g.grp_out + g.dup_off + t;
-      row = bag * g.grp_out + g.out_off + t;
-    }
-    const bool vec = ne == 8 && g.ldc % 8 == 0 && (!g.pre || g.ld_pre % 8 == 0);
-    const size_t off = (size_t)row * g.ldc + n;
-    float addr[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, addc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (g.resid) {
-      if (vec) { const f32x8 t8 = load8<float>(g.resid + off); for (int e = 0; e < 8; ++e) addr[e] = t8[e]; }
-      else { for (int e = 0; e < ne; ++e) addr[e] = g.resid[off + e]; }
-    }
-    if (g.accumulate) {
-      if (vec) { const vec8<OutT> t8 = load8<OutT>(C + off); for (int e = 0; e < 8; ++e) addc[e] = to_f(t8[e]); }
-      else { for (int e = 0; e < ne; ++e) addc[e] = to_f(C[off + e]); }
-    }
-    float x[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) x[e] = v[e] * g.alpha + bv[e];
-    vec8<OutT> pre8, out8;
-    if (g.pre) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) pre8[e] = from_f<OutT>(x[e]);
-    }
-    if (g.gelu) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = gelu_erf(x[e]);
-    }
-    if (g.drop_p > 0.f) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float u = dropout_u01(seed, (uint32_t)row, (uint32_t)(n + e));
-        x[e] = (u >= g.drop_p) ? x[e] * g.drop_scale : 0.f;
-      }
-    }
-    // as gemm_epilogue_rows: + residual, then + the stored C (accumulate), in that order
-    if (g.resid) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] += addr[e];
-    }
-    if (g.accumulate) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] += addc[e];
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) out8[e] = from_f<OutT>(x[e]);
-    if (vec) {
-      if (g.pre) store8<OutT>((OutT*)g.pre + (size_t)m * g.ld_pre + n, pre8);
-      store8<OutT>(C + off, out8);
-      if (dup >= 0) store8<OutT>(C + (size_t)dup * g.ldc + n, out8);
-    } else {
-      for (int e = 0; e < ne; ++e) {
-        if (g.pre) ((OutT*)g.pre)[(size_t)m * g.ld_pre + n + e] = pre8[e];
-        C[off + e] = out8[e];
-        if (dup >= 0) C[(size_t)dup * g.ldc + n + e] = out8[e];
-      }
-    }
-  }
-}
-
-template <typename OutT, bool B_KN, int KIND>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void gemm_pr_kernel(
-    const bf16* __restrict__ A, const bf16* __restrict__ B, OutT* __restrict__ C, tm_gemm_args g, int tiles_m,
-    int tiles_n) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 1, wn = wave & 1;   // 4 (M) x 2 (N) waves of 32 x 64
-  const int ntiles = tiles_m * tiles_n;       // splits == 1 (host-checked)
-
-  unsigned akc[4], bkc0[4] = {0, 0, 0, 0}, bkc1[4] = {0, 0, 0, 0};
-  unsigned bks0 = 0, bks1 = 0;
-  kc_addrs(akc, wm * 32, lane);
-  if constexpr (B_KN) {
-    bks0 = ks_addr(wn * 64, lane) + STAGE_BYTES / 2;
-    bks1 = ks_addr(wn * 64 + 32, lane) + STAGE_BYTES / 2;
-  } else {
-    kc_addrs(bkc0, wn * 64, lane);
-    kc_addrs(bkc1, wn * 64 + 32, lane);
-#pragma unroll
-    for (int s = 0; s < 4; ++s) { bkc0[s] += STAGE_BYTES / 2; bkc1[s] += STAGE_BYTES / 2; }
-  }
-  const unsigned ring = lds_u32(smem);
-  const uint64_t seed = (KIND == EK_ANY && g.drop_p > 0.f) ? effective_seed(g.seed, g.seed_ptr) : 0;
-
-  PTile is{}, cs{};
-  is.i = 0;
-  ptile_set(is, ntiles, tiles_m, tiles_n, g);
-  cs = is;
-  int issued = 0, done = 0;
-  auto issue = [&]() {
-    char* st = smem + (issued % PR_NS) * STAGE_BYTES;
-    const int k0 = is.kt * 64;
-    glds_tile<false>(st, A, g.lda, is.m0, g.M, k0, wave, lane);
-    glds_tile<B_KN>(st + STAGE_BYTES / 2, B, g.ldb, is.n0, g.N, k0, wave, lane);
-    ++issued;
-    if (++is.kt == is.nk) { ++is.i; ptile_set(is, ntiles, tiles_m, tiles_n, g); }
-  };
-  if (is.t < ntiles) issue();
-
-  f32x16 acc[2];
-  acc[0] = (f32x16){};
-  acc[1] = (f32x16){};
-  const int h = lane >> 5, r32 = lane & 31;
-  while (cs.t < ntiles) {
-    // step `done` landed once at most (issued - done - 1) younger steps (4 loads each) remain; after
-    // an epilogue none is younger, and the wait also retires that epilogue's stores
-    if (issued - done - 1 >= 1) wait_vm<4>(); else wait_vm<0>();
-    __builtin_amdgcn_s_barrier();  // every wave's pieces landed; every wave done with step done-1
-    asm volatile("" ::: "memory");
-    if (is.t < ntiles) issue();    // overwrites step done-1's slot (possibly the next tile's first step)
-    const unsigned sb = ring + (done % PR_NS) * STAGE_BYTES;
-    ring_tile_mma<false, B_KN, true>(acc, sb, (B_KN ? bks0 : 0) + sb, (B_KN ? bks1 : 0) + sb, akc, bkc0, bkc1);
-    ++done;
-    if (++cs.kt == cs.nk) {
-      // epilogue from registers: acc[j] lane l = row 32 wm + r32 (of the tile), columns
-      // 64 wn + 32 j + acc_row(i, h); the (l, l ^ 32) exchange gives 8 consecutive columns
-      const int m = cs.m0 + wm * 32 + r32;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-          const int q0 = 2 * p, q1 = 2 * p + 1;
-          float send[4], recv[4], v[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) send[e] = h ? acc[j][4 * q0 + e] : acc[j][4 * q1 + e];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) recv[e] = __shfl_xor(send[e], 32, 64);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            v[e] = h ? recv[e] : acc[j][4 * q0 + e];
-            v[4 + e] = h ? acc[j][4 * q1 + e] : recv[e];
-          }
-          pr_epilogue_chunk<OutT, KIND>(C, g, m, cs.n0 + wn * 64 + j * 32 + 16 * p + 8 * h, v, seed);
-        }
-      }
-      acc[0] = (f32x16){};
-      acc[1] = (f32x16){};
-      ++cs.i;
-      ptile_set(cs, ntiles, tiles_m, tiles_n, g);
-    }
-  }
-}
-#endif  // TM_DIAG (gemm_pr_kernel: measured slower on every step shape, profiles/r05d_ab_gemm_pr_rejected.txt)
-
-// ---------------------------------------------------------------------------
 // Big-tile bf16 GEMM: 256 x TBN (256 or 128) per 512-thread workgroup.  A 128 x 128 tile moves
 // 32 KB of operands per 64-deep k-step for 2 MFLOP (64 flop/B): at 2.5 PF that needs ~39 TB/s of
 // L2 -> CU operand bandwidth, which the chip does not have (the 128-tile kernels above run at
@@ -1272,7 +930,7 @@ TM_DEV void rd_big(bf16x8& f, unsigned base, unsigned kc_s) {
 }
 
 constexpr int BIG_EROWS = 128;   // rows per epilogue pass of the big-tile kernel
-template <typename OutT, bool A_T, bool B_KN, int TBN, bool STAMP = false>   // STAMP: diagnostic variant 12
+template <typename OutT, bool A_T, bool B_KN, int TBN, bool STAMP = false>   // STAMP: diagnostic build only
 __global__ __launch_bounds__(512) void gemm_big_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
                                                        OutT* __restrict__ C, tm_gemm_args g) {
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1418,26 +1076,32 @@ constexpr int big_lds() {
   return ring > epi ? ring : epi;
 }
 
-template <typename T, bool A_T, bool B_KN, int NBUF = 2>
+template <typename T, bool A_T, bool B_KN>
 constexpr size_t gemm_smem() {
-  constexpr size_t main = NBUF * (tile_elems<T, A_T>() + tile_elems<T, B_KN>()) * sizeof(T);
+  constexpr size_t main = (tile_elems<T, A_T>() + tile_elems<T, B_KN>()) * sizeof(T);
   constexpr size_t epi = (size_t)(BM / 2) * EP_ROW * sizeof(float);
   return main > epi ? main : epi;
 }
 
-// 0 = the 2-stage 128 x 128 DMA ring where it applies (bf16, 64 | K per split), else the
-// register-staged loop with 1 LDS buffer; 1 = register-staged, 2 LDS buffers; 2 = 4-stage ring;
-// 3 = register-staged, 1 LDS buffer; 4 = persistent 128 x 128 DMA ring; 5 = 2-stage ring; 6 =
-// 3-stage ring; 7 = 256 x 256 / 256 x 128 big-tile kernel.  The 2-stage ring (69.6 KB of LDS with
-// its epilogue image) keeps two workgroups per CU, which is what wins on these shapes: at
-// M = 8448 rows 264 tiles of 128 x 128 are a 256-CU wave plus 8 tiles, and the second workgroup
-// on a CU shares its operand intake instead of waiting for a second round (QKV 32.2 vs 36.5 us
-// big-tile; to_out 17.9 vs 21.0 register-staged; dxn 31.1 vs 36.4; fc1 18.3 vs 25.3; weight
-// grads 19.3 / 35.6 / 29.1 vs 21.5 / 39.1 / 38.1; scripts/dev/gemm_shapes.py)
+// ---------------------------------------------------------------------------
+// Host dispatch.  bf16 GEMMs run on one of four kernels; fp32 (parity mode) on the last only:
+//   big tile   256 x 256 / 256 x 128, for to_qkv (big_pays)
+//   ring160    160 x 128 LDS-DMA ring where it saves a round of tiles (ring160_pays)
+//   ring       128 x 128 LDS-DMA ring wherever its shape conditions hold (ring_ok).  69.6 KB of LDS
+//              with the epilogue image keeps two workgroups per CU: at M = 8448 rows 264 tiles are a
+//              256-CU wave plus 8, and the second workgroup on a CU shares its operand intake
+//   reg        register-staged loop, any shape
+enum GemmPath { PATH_BIG, PATH_RING160, PATH_RING, PATH_REG };
+
+// Selectors of the diagnostic build (tm_debug_set_gemm_sel; GEMM_SEL in scripts/microbench.py):
+// a path forced wherever it is valid (the ring otherwise), or the product's pick with the
+// stamped instantiation of the ring / big-tile kernel.  The product build compiles GEMM_AUTO in.
+enum GemmSel { GEMM_AUTO = 0, GEMM_FORCE_REG, GEMM_FORCE_RING, GEMM_FORCE_RING160, GEMM_FORCE_BIG,
+               GEMM_STAMP_RING, GEMM_STAMP_BIG };
 #ifdef TM_DIAG
-int g_gemm_variant = 0;
+int g_gemm_sel = GEMM_AUTO;
 #endif
-#define GEMM_VARIANT TM_DIAG_VAR(g_gemm_variant)
+#define GEMM_SEL TM_DIAG_VAR(g_gemm_sel)
 
 // the specialised epilogue a launch can use (EK_ANY keeps the runtime-mode one)
 inline int epilogue_kind(const tm_gemm_args& g) {
@@ -1447,9 +1111,7 @@ inline int epilogue_kind(const tm_gemm_args& g) {
   return EK_ANY;
 }
 
-template <typename OutT>
-bool ring_ok(const tm_gemm_args& g) {
-  if (GEMM_VARIANT != 0 && GEMM_VARIANT != 8 && GEMM_VARIANT != 9 && (GEMM_VARIANT < 2 || GEMM_VARIANT > 6 || GEMM_VARIANT == 3)) return false;
+inline bool ring_ok(const tm_gemm_args& g) {
   // whole 64-deep k-tiles in every split; k-strided operands need >= 8 rows/cols (clamped 16-B pieces)
   if (g.K % 64 != 0 || (g.splits > 1 && g.k_per_split % 64 != 0)) return false;
   if ((g.a_trans && g.M < 8) || (g.b_kn && g.N < 8)) return false;
@@ -1458,218 +1120,109 @@ bool ring_ok(const tm_gemm_args& g) {
   return true;
 }
 
-// 160-row tiles (k-contiguous A, no split)
-// (diagnostic build: variant 9 never, 10 wherever valid)
-inline bool use_ring160(const tm_gemm_args& g) {
+// 160-row tiles: k-contiguous A, no split
+inline bool ring160_ok(const tm_gemm_args& g) {
   if (g.a_trans || g.splits != 1 || g.K % 64 != 0 || g.M < BM160 || g.mode == TM_EPI_SPLITK) return false;
   if (g.b_kn && (g.N % 8 != 0 || g.N < 8)) return false;
-  if (GEMM_VARIANT == 10) return true;
-  if (GEMM_VARIANT != 0) return false;
+  return true;
+}
+inline bool ring160_pays(const tm_gemm_args& g) {
   // the heavy runtime-mode epilogue (dropout hash, residual, row map: to_out) stays on 128-row
   // tiles: in the step it ran 22.6 vs 20 us there (three staging passes of 512 of 640 threads)
   if (epilogue_kind(g) == EK_ANY) return false;
   // where 128-row tiles spill past one per CU and 160-row tiles do not (N = 512 at 8448 rows: dxn
   // 28.8 -> 22.9 us, to_out 16.2 -> 13.9, dmerged 13.3 -> 11.4); at N = 1536 (QKV, 3.1 vs 2.5 tiles
-  // per CU) the 128-row ring stays faster (24.5 vs 27.6 us; scripts/dev/gemm_variants.py 9,10)
+  // per CU) the 128-row ring stays faster (24.5 vs 27.6 us)
   const long long tn = (g.N + BN - 1) / BN;
   const long long t128 = (g.M + 127) / 128 * tn, t160 = (g.M + BM160 - 1) / BM160 * tn;
   const long long cu = tm_cu_count();
   return t128 > cu && t160 <= cu;
 }
 
-#ifdef TM_DIAG
-// the persistent register-epilogue kernel (k-contiguous A, no split): diagnostic build only, variant
-// 11 wherever valid (the product library never selects it: slower on every step shape)
-inline bool use_pr(const tm_gemm_args& g) {
-  if (g.a_trans || g.splits != 1 || g.K % 64 != 0 || g.mode == TM_EPI_SPLITK || g.pre_bf16) return false;
-  if (g.b_kn && (g.N % 8 != 0 || g.N < 8)) return false;
-  return GEMM_VARIANT == 11;
-}
-#endif
-
-// the big-tile kernel's valid shapes; selected for every valid GEMM by diagnostic variant 7, and in the
-// product for the to_qkv projection (head-major scatter epilogue, N >= 1024, no split): 198 tiles of
-// 256 x 256 at n' = 8448 fill the chip in one round where the 128 x 128 ring needed 1.55 rounds of
-// 792 tiles (microbench 23.2 vs 27.6 us; scripts/microbench.py --gemm-ab)
-inline bool qkv_big_enabled() {   // TM_GEMM_QKV_BIG=0: the 128 x 128 ring for to_qkv (A/B runs only)
-  static const bool on = [] { const char* e = std::getenv("TM_GEMM_QKV_BIG"); return !(e && e[0] == '0'); }();
-  return on;
-}
-template <typename OutT>
-bool big_ok(const tm_gemm_args& g) {
-  const bool qkv_pick = (GEMM_VARIANT == 0 || GEMM_VARIANT == 12) && g.mode == TM_EPI_QKV && g.N >= 1024 && g.splits == 1 && g.M >= 2048 &&
-                        !g.a_trans && !g.b_kn && qkv_big_enabled();
-  if (GEMM_VARIANT != 7 && !qkv_pick) return false;
+inline bool big_ok(const tm_gemm_args& g) {
   if (g.K % 64 != 0 || (g.splits > 1 && g.k_per_split % 64 != 0)) return false;
   if (g.a_trans && (g.M % 8 != 0 || g.M < 8)) return false;
   if (g.b_kn && (g.N % 8 != 0 || g.N < 8)) return false;
   return g.M >= 128 && g.N >= 128;
 }
+// the to_qkv projection (head-major scatter epilogue, N >= 1024, no split): 198 tiles of 256 x 256
+// at n' = 8448 fill the chip in one round where the 128 x 128 ring needed 1.55 rounds of 792 tiles
+// (microbench 23.2 vs 27.6 us; scripts/microbench.py --gemm-ab)
+inline bool big_pays(const tm_gemm_args& g) {
+  return g.mode == TM_EPI_QKV && g.N >= 1024 && g.splits == 1 && g.M >= 2048 && !g.a_trans && !g.b_kn;
+}
+
+inline GemmPath pick_path(const tm_gemm_args& g) {   // bf16 operands
+  const int sel = GEMM_SEL;
+  const bool product = sel == GEMM_AUTO || sel == GEMM_STAMP_BIG;
+  if (big_ok(g) && (sel == GEMM_FORCE_BIG || (product && big_pays(g)))) return PATH_BIG;
+  if (ring160_ok(g) && (sel == GEMM_FORCE_RING160 || (product && ring160_pays(g)))) return PATH_RING160;
+  if (ring_ok(g) && sel != GEMM_FORCE_REG) return PATH_RING;
+  return PATH_REG;
+}
+
+// the ring / big-tile kernel of a launch: the stamped instantiation where the diagnostic build asks
+template <typename OutT, bool AT, bool BKN, int KIND>
+auto ring_kernel() {
+#ifdef TM_DIAG
+  if (g_gemm_sel == GEMM_STAMP_RING) return gemm_ring_kernel<OutT, AT, BKN, true>;
+#endif
+  return gemm_ring_kernel<OutT, AT, BKN, false, KIND>;
+}
+template <typename OutT, bool AT, bool BKN, int TBN>
+auto big_kernel() {
+#ifdef TM_DIAG
+  if (g_gemm_sel == GEMM_STAMP_BIG) return gemm_big_kernel<OutT, AT, BKN, TBN, true>;
+#endif
+  return gemm_big_kernel<OutT, AT, BKN, TBN>;
+}
+
+// f(A_T, B_KN, KIND) as compile-time constants for the launch's (a_trans, b_kn, epilogue kind)
+template <typename F>
+int with_flags(const tm_gemm_args& g, F&& f) {
+  auto with_kind = [&](auto at, auto bkn) {
+    switch (epilogue_kind(g)) {
+      case EK_PLAIN: return f(at, bkn, std::integral_constant<int, EK_PLAIN>{});
+      case EK_QKV: return f(at, bkn, std::integral_constant<int, EK_QKV>{});
+      case EK_SPLITK: return f(at, bkn, std::integral_constant<int, EK_SPLITK>{});
+      default: return f(at, bkn, std::integral_constant<int, EK_ANY>{});
+    }
+  };
+  if (g.a_trans) return g.b_kn ? with_kind(std::true_type{}, std::true_type{}) : with_kind(std::true_type{}, std::false_type{});
+  return g.b_kn ? with_kind(std::false_type{}, std::true_type{}) : with_kind(std::false_type{}, std::false_type{});
+}
 
 template <typename T, typename OutT>
 int launch_t(const void* A, const void* B, void* C, const tm_gemm_args& g, hipStream_t st) {
-  dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, g.splits);
-  if constexpr (sizeof(T) == 2) {
-    if (big_ok<OutT>(g)) {
-#ifdef TM_DIAG
-#define TM_BIG_STAMP(AT, BKN, TBN)                                                                   \
-      if (GEMM_VARIANT == 12) {   /* diagnostic: the QKV pick with per-workgroup stamps */         \
-        tm_allow_smem(gemm_big_kernel<OutT, AT, BKN, TBN, true>, sm);                                \
-        gemm_big_kernel<OutT, AT, BKN, TBN, true><<<gb, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-      } else
-#else
-#define TM_BIG_STAMP(AT, BKN, TBN)
-#endif
-#define TM_BIG_CASE(AT, BKN, TBN)                                                                  \
-      if (g.a_trans == AT && g.b_kn == BKN) {                                                      \
-        constexpr int sm = big_lds<OutT, TBN>();                                                   \
-        tm_allow_smem(gemm_big_kernel<OutT, AT, BKN, TBN>, sm);                                   \
-        const dim3 gb((g.N + TBN - 1) / TBN, (g.M + GBM - 1) / GBM, g.splits);                      \
-        TM_BIG_STAMP(AT, BKN, TBN)                                                                 \
-        gemm_big_kernel<OutT, AT, BKN, TBN><<<gb, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-        TM_CHECK_LAUNCH();                                                                         \
-        return 0;                                                                                  \
+  if ((unsigned)g.a_trans > 1u || (unsigned)g.b_kn > 1u) {
+    tm_set_error("gemm: bad transpose flags");
+    return 1;
+  }
+  const GemmPath path = sizeof(T) == 2 ? pick_path(g) : PATH_REG;
+  // one launch: `kernel` over tile_m x tile_n tiles (and the splits)
+  auto run = [&](auto kernel, int tile_m, int tile_n, int threads, size_t lds) {
+    const dim3 grid((g.N + tile_n - 1) / tile_n, (g.M + tile_m - 1) / tile_m, g.splits);
+    tm_allow_smem(kernel, lds);
+    kernel<<<grid, threads, lds, st>>>((const T*)A, (const T*)B, (OutT*)C, g);
+    TM_CHECK_LAUNCH();
+    return 0;
+  };
+  return with_flags(g, [&](auto at, auto bkn, auto kind) {
+    constexpr bool AT = decltype(at)::value, BKN = decltype(bkn)::value;
+    constexpr int KIND = decltype(kind)::value;
+    if constexpr (sizeof(T) == 2) {
+      if (path == PATH_BIG) {
+        if (g.N >= 1024) return run(big_kernel<OutT, AT, BKN, 256>(), GBM, 256, 512, big_lds<OutT, 256>());
+        return run(big_kernel<OutT, AT, BKN, 128>(), GBM, 128, 512, big_lds<OutT, 128>());
       }
-      if (g.N >= 1024) {
-        TM_BIG_CASE(0, 0, 256) TM_BIG_CASE(0, 1, 256) TM_BIG_CASE(1, 0, 256) TM_BIG_CASE(1, 1, 256)
-      } else {
-        TM_BIG_CASE(0, 0, 128) TM_BIG_CASE(0, 1, 128) TM_BIG_CASE(1, 0, 128) TM_BIG_CASE(1, 1, 128)
+      if constexpr (!AT && KIND != EK_SPLITK) {   // ring160_ok
+        if (path == PATH_RING160) return run(gemm_ring160_kernel<OutT, BKN, KIND>, BM160, BN, 640, 2 * R160_STAGE);
       }
-#undef TM_BIG_STAMP
-#undef TM_BIG_CASE
-    }
-#ifdef TM_DIAG
-    if (ring_ok<OutT>(g) && GEMM_VARIANT == 4) {
-      const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-      const int ntiles = tiles_m * tiles_n * g.splits;
-      const int nwg = ntiles < 256 ? ntiles : 256;
-#define TM_PERSIST_CASE(AT, BKN)                                                                \
-      if (g.a_trans == AT && g.b_kn == BKN) {                                                   \
-        tm_allow_smem(gemm_persist_kernel<OutT, AT, BKN>, PERSIST_LDS);                         \
-        gemm_persist_kernel<OutT, AT, BKN><<<nwg, 512, PERSIST_LDS, st>>>((const bf16*)A, (const bf16*)B, \
-                                                                        (OutT*)C, g, tiles_m, tiles_n); \
-        TM_CHECK_LAUNCH();                                                                      \
-        return 0;                                                                               \
-      }
-      TM_PERSIST_CASE(0, 0) TM_PERSIST_CASE(0, 1) TM_PERSIST_CASE(1, 0) TM_PERSIST_CASE(1, 1)
-#undef TM_PERSIST_CASE
-    }
-    if (use_pr(g)) {
-      const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.N + BN - 1) / BN;
-      const int ntiles = tiles_m * tiles_n, cap = 2 * tm_cu_count();
-      const int nwg = ntiles < cap ? ntiles : cap;
-      const int kind = epilogue_kind(g);
-#define TM_PR(BKN, K)                                                                                \
-      {                                                                                              \
-        tm_allow_smem(gemm_pr_kernel<OutT, BKN, K>, PR_LDS);                                         \
-        gemm_pr_kernel<OutT, BKN, K><<<nwg, 512, PR_LDS, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g, \
-                                                              tiles_m, tiles_n);                     \
-      }
-      if (g.b_kn) {
-        if (kind == EK_PLAIN) TM_PR(true, EK_PLAIN) else if (kind == EK_QKV) TM_PR(true, EK_QKV) else TM_PR(true, EK_ANY)
-      } else {
-        if (kind == EK_PLAIN) TM_PR(false, EK_PLAIN) else if (kind == EK_QKV) TM_PR(false, EK_QKV) else TM_PR(false, EK_ANY)
-      }
-#undef TM_PR
-      TM_CHECK_LAUNCH();
-      return 0;
-    }
-#endif
-    if (use_ring160(g)) {
-      constexpr size_t sm = 2 * R160_STAGE;
-      const dim3 g160((g.N + BN - 1) / BN, (g.M + BM160 - 1) / BM160);
-      const int kind = epilogue_kind(g);
-#define TM_R160(BKN, K)                                                                             \
-      {                                                                                             \
-        tm_allow_smem(gemm_ring160_kernel<OutT, BKN, K>, sm);                                       \
-        gemm_ring160_kernel<OutT, BKN, K><<<g160, 640, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-      }
-      if (g.b_kn) {
-        if (kind == EK_PLAIN) TM_R160(true, EK_PLAIN) else if (kind == EK_QKV) TM_R160(true, EK_QKV) else TM_R160(true, EK_ANY)
-      } else {
-        if (kind == EK_PLAIN) TM_R160(false, EK_PLAIN) else if (kind == EK_QKV) TM_R160(false, EK_QKV) else TM_R160(false, EK_ANY)
-      }
-#undef TM_R160
-      TM_CHECK_LAUNCH();
-      return 0;
-    }
-    if (ring_ok<OutT>(g)) {
       constexpr size_t epi = (size_t)BM * EP_ROW * sizeof(float);
-#ifdef TM_DIAG
-#define TM_RING_DIAG(AT, BKN)                                                                   \
-        else if (GEMM_VARIANT == 8) {                                                       \
-          constexpr size_t sm = 2 * STAGE_BYTES > epi ? 2 * STAGE_BYTES : epi;                  \
-          tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 2, true>, sm);                          \
-          gemm_ring_kernel<OutT, AT, BKN, 2, true><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-        } else if (GEMM_VARIANT == 6) {                                                       \
-          constexpr size_t sm = 3 * STAGE_BYTES > epi ? 3 * STAGE_BYTES : epi;                  \
-          tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 3>, sm);                                \
-          gemm_ring_kernel<OutT, AT, BKN, 3><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-        } else {                                                                                \
-          constexpr size_t sm = RING_BYTES > epi ? RING_BYTES : epi;                            \
-          tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN>, sm);                                   \
-          gemm_ring_kernel<OutT, AT, BKN><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-        }
-#else
-#define TM_RING_DIAG(AT, BKN)
-#endif
-#define TM_RING_CASE(AT, BKN)                                                                   \
-      if (g.a_trans == AT && g.b_kn == BKN) {                                                   \
-        if (GEMM_VARIANT == 0 || GEMM_VARIANT == 5 || GEMM_VARIANT == 9) {                  \
-          constexpr size_t sm = 2 * STAGE_BYTES > epi ? 2 * STAGE_BYTES : epi;                  \
-          const int kind = epilogue_kind(g);                                                    \
-          if (kind == EK_PLAIN) {                                                               \
-            tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_PLAIN>, sm);             \
-            gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_PLAIN><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-          } else if (kind == EK_QKV) {                                                          \
-            tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_QKV>, sm);               \
-            gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_QKV><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-          } else if (kind == EK_SPLITK) {                                                       \
-            tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_SPLITK>, sm);            \
-            gemm_ring_kernel<OutT, AT, BKN, 2, false, EK_SPLITK><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-          } else {                                                                              \
-            tm_allow_smem(gemm_ring_kernel<OutT, AT, BKN, 2>, sm);                              \
-            gemm_ring_kernel<OutT, AT, BKN, 2><<<grid, 512, sm, st>>>((const bf16*)A, (const bf16*)B, (OutT*)C, g); \
-          }                                                                                     \
-        }                                                                                       \
-        TM_RING_DIAG(AT, BKN)                                                                   \
-        TM_CHECK_LAUNCH();                                                                      \
-        return 0;                                                                               \
-      }
-      TM_RING_CASE(0, 0) TM_RING_CASE(0, 1) TM_RING_CASE(1, 0) TM_RING_CASE(1, 1)
-#undef TM_RING_CASE
-#undef TM_RING_DIAG
+      if (path == PATH_RING) return run(ring_kernel<OutT, AT, BKN, KIND>(), BM, BN, 512, RING_BYTES > epi ? RING_BYTES : epi);
     }
-  }
-  const T* a = (const T*)A;
-  const T* b = (const T*)B;
-  OutT* c = (OutT*)C;
-#ifdef TM_DIAG
-#define TM_GEMM_2BUF(AT, BKN)                                                       \
-    if (GEMM_VARIANT == 1) {                                                        \
-      constexpr size_t sm = gemm_smem<T, AT, BKN>();                                \
-      tm_allow_smem(gemm_kernel<T, OutT, AT, BKN>, sm);                             \
-      gemm_kernel<T, OutT, AT, BKN><<<grid, 256, sm, st>>>(a, b, c, g);             \
-      TM_CHECK_LAUNCH();                                                            \
-      return 0;                                                                     \
-    }
-#else
-#define TM_GEMM_2BUF(AT, BKN)
-#endif
-#define TM_GEMM_CASE(AT, BKN)                                                       \
-  if (g.a_trans == AT && g.b_kn == BKN) {                                           \
-    TM_GEMM_2BUF(AT, BKN)                                                           \
-    constexpr size_t sm = gemm_smem<T, AT, BKN, 1>();                               \
-    tm_allow_smem(gemm_kernel<T, OutT, AT, BKN, 1>, sm);                            \
-    gemm_kernel<T, OutT, AT, BKN, 1><<<grid, 256, sm, st>>>(a, b, c, g);            \
-    TM_CHECK_LAUNCH();                                                              \
-    return 0;                                                                       \
-  }
-  TM_GEMM_CASE(0, 0) TM_GEMM_CASE(0, 1) TM_GEMM_CASE(1, 0) TM_GEMM_CASE(1, 1)
-#undef TM_GEMM_CASE
-#undef TM_GEMM_2BUF
-  tm_set_error("gemm: bad transpose flags");
-  return 1;
+    return run(gemm_kernel<T, OutT, AT, BKN>, BM, BN, 256, gemm_smem<T, AT, BKN>());
+  });
 }
 
 // out = alpha * sum_z slab[z] (+ out): the splits are summed in index order (bitwise
@@ -1746,7 +1299,7 @@ extern "C" int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args
   if (g->M == 0 || g->N == 0) return 0;
   // the fused bias-gradient column sums ride in the bf16 ring kernel's split-K weight-gradient form only
   TM_REQUIRE(!g->colsum || (g->ab_dtype == TM_BF16 && g->c_dtype == TM_F32 && g->a_trans && g->mode == TM_EPI_SPLITK &&
-                            ring_ok<float>(*g) && (GEMM_VARIANT == 0 || GEMM_VARIANT == 5 || GEMM_VARIANT == 9)),
+                            pick_path(*g) == PATH_RING && GEMM_SEL != GEMM_STAMP_RING),
              "gemm: colsum needs the bf16 split-K weight-gradient ring path (a_trans, K % 64 == 0, M % 8 == 0)");
   hipStream_t st = (hipStream_t)stream;
   if (g->ab_dtype == TM_BF16) {
@@ -1761,9 +1314,9 @@ extern "C" int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args
 }
 
 #ifdef TM_DIAG
-extern "C" void tm_debug_set_gemm_variant(int value) { g_gemm_variant = value; }
+extern "C" void tm_debug_set_gemm_sel(int sel) { g_gemm_sel = sel; }   // a GemmSel
 
-// copy the variant-8 ring stamps ([block][8] u64) to a host buffer (diagnostics only)
+// copy the ring / big-tile stamps ([block][8] u64) to a host buffer (diagnostics only)
 extern "C" int tm_debug_gemm_stamps(unsigned long long* host, int count) {
   TM_REQUIRE(count > 0 && count <= 2048 * 8, "gemm_stamps: bad count");
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_gemm_stamps), count * sizeof(unsigned long long)) != hipSuccess) {

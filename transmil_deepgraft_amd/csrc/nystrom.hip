@@ -216,83 +216,6 @@ __global__ __launch_bounds__(256) void sim2_softmax_kernel(const float* __restri
 // columns 32 w .. 32 w + 31 (one 32x32 tile, 4 k-steps x 3 MFMAs).  Every operand load is issued
 // before the first MFMA (64 floats per lane); row max / sum: 32-lane shuffles, then the 8 waves'
 // partials through LDS in a fixed order.  Writes A2 (fp32) and its hi / lo planes.
-#ifdef TM_DIAG
-__global__ __launch_bounds__(512) void sim2_softmax_mfma_kernel(const float* __restrict__ ql,
-                                                                const float* __restrict__ kl, float* __restrict__ a2,
-                                                                bf16* __restrict__ a2s) {
-  __shared__ float red[2][8][32];
-  const int bh = blockIdx.x, r0 = blockIdx.y * 32, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int r = lane & 31, h = lane >> 5, c0 = wave * 32;
-  const float* qa = ql + ((size_t)bh * NL + r0 + r) * DH + 8 * h;
-  const float* kb = kl + ((size_t)bh * NL + c0 + r) * DH + 8 * h;
-  f32x4 av[8], bv[8];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    av[2 * s] = *(const f32x4*)(qa + 16 * s);
-    av[2 * s + 1] = *(const f32x4*)(qa + 16 * s + 4);
-    bv[2 * s] = *(const f32x4*)(kb + 16 * s);
-    bv[2 * s + 1] = *(const f32x4*)(kb + 16 * s + 4);
-  }
-  f32x16 acc = (f32x16){};
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    bf16x8 ah, al, bhi, blo;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float x = e < 4 ? av[2 * s][e] : av[2 * s + 1][e - 4];
-      const float y = e < 4 ? bv[2 * s][e] : bv[2 * s + 1][e - 4];
-      ah[e] = (bf16)x;
-      al[e] = (bf16)(x - (float)ah[e]);
-      bhi[e] = (bf16)y;
-      blo[e] = (bf16)(y - (float)bhi[e]);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bhi, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, blo, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bhi, acc, 0, 0, 0);
-  }
-  // row i (reg i, half h) holds columns c0 + (lane & 31): max / sum over the 32 lanes of the half
-  auto half_max = [](float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
-  };
-  auto half_sum = [](float v) {
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const float m = half_max(acc[i]);
-    if (r == 0) red[0][wave][acc_row(i, h)] = m;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = acc_row(i, h);
-    float m = red[0][0][row];
-#pragma unroll
-    for (int w = 1; w < 8; ++w) m = fmaxf(m, red[0][w][row]);
-    acc[i] = __expf(acc[i] - m);
-    const float t = half_sum(acc[i]);
-    if (r == 0) red[1][wave][row] = t;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int row = acc_row(i, h);
-    const float tot = ((red[1][0][row] + red[1][1][row]) + (red[1][2][row] + red[1][3][row])) +
-                      ((red[1][4][row] + red[1][5][row]) + (red[1][6][row] + red[1][7][row]));
-    const size_t o = ((size_t)bh * NL + r0 + row) * NL + c0 + r;
-    const float v = acc[i] / tot;
-    a2[o] = v;
-    const bf16 hi = (bf16)v;
-    a2s[o] = hi;
-    a2s[o + (size_t)gridDim.x * NL * NL] = (bf16)(v - (float)hi);
-  }
-}
-
-#endif  // TM_DIAG
 
 // dS2 = A2 * (dA2 - rowsum(dA2 * A2)); grid (nbh*256/4), block 256 (one wave per row)
 __global__ void softmax_bwd_rows_kernel(const float* __restrict__ a, const float* __restrict__ da,
@@ -463,7 +386,7 @@ constexpr int A1_VS = 66;  // conv window row stride (floats): a wave's 2 query 
 constexpr int A1_WIN_ITEMS = (128 + 2 * HALF) * 8 / 256;
 constexpr size_t A1_EPI_BYTES = (128 * 68 + (128 + 2 * HALF) * A1_VS) * sizeof(float);
 
-template <typename T, int VAR = 0>   // VAR (ablation): 1 = no conv taps, 2 = no MFMA phase
+template <typename T>
 __global__ __launch_bounds__(256, 2) void a1_fwd_kernel(const T* __restrict__ q, const T* __restrict__ v,
                                                      const T* __restrict__ kl_t, const T* __restrict__ y_t,
                                                      const float* __restrict__ wconv, int n, int nh,
@@ -510,12 +433,7 @@ __global__ __launch_bounds__(256, 2) void a1_fwd_kernel(const T* __restrict__ q,
   __syncthreads();
   f32x16 o[2];
   float mx, sum;
-  if constexpr (VAR == 2) {
-    o[0] = (f32x16){}; o[1] = (f32x16){};
-    mx = to_f(qf[0][0]); sum = 1.f + to_f(ks[lane]) + to_f(vt[lane]);
-  } else {
-    attn_fwd_wave<T>(ks, vt, qf, o, mx, sum, lane);
-  }
+  attn_fwd_wave<T>(ks, vt, qf, o, mx, sum, lane);
   if (h == 0) lse1[(size_t)bh * n + qrow] = mx + __logf(sum);
   const float inv = 1.0f / sum;
   // the conv window is requested now, overlapping the normalisation / LDS round trip below
@@ -542,7 +460,7 @@ __global__ __launch_bounds__(256, 2) void a1_fwd_kernel(const T* __restrict__ q,
   __syncthreads();
   // conv residual, register-blocked: thread = (16 consecutive queries, 2 d); every window
   // row is read once from LDS and feeds up to 16 outputs.
-  if constexpr (VAR != 1) {
+  {
     const int dp = tid & 31, qb = tid >> 5;
     const float* wc = wconv + head * TAPS;
     float w[TAPS];
@@ -607,11 +525,11 @@ constexpr size_t A1P_BAND_OFF = A1P_OST_OFF + A1P_WAVES * A1P_OST;      // [4][6
 constexpr size_t A1P_TAPS_OFF = A1P_BAND_OFF + 4 * 64 * 16;
 constexpr size_t A1P_BYTES = A1P_TAPS_OFF + 128 * sizeof(float);        // 162304
 
-// diagnostic stamps (VAR 9 build only): [block][wave][slot] s_memtime, read by tm_debug_a1_stamps
+// diagnostic stamps (STAMP instantiations only): [block][wave][slot] s_memtime, read by tm_debug_a1_stamps
 __device__ unsigned long long g_a1_stamps[512 * 8 * 8];
-template <int VAR>
+template <bool STAMP>
 TM_DEV void a1p_stamp(int slot, int wave) {
-  if constexpr (VAR == 9) {
+  if constexpr (STAMP) {
     __builtin_amdgcn_sched_barrier(0);
     unsigned long long t;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
@@ -637,52 +555,13 @@ TM_DEV bf16x8 a1p_window_frag(const bf16* win, int dt, int kb, int lane) {
   return (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 
-// attn_fwd_wave with the per-tile work interleaved for the scheduler: the max tree of score
-// tile kt beside the MFMAs of tile kt + 1, the exp / sum / bf16 packing of tile kt beside its
-// P.V MFMAs (the two-phase form ran the MFMA and VALU phases back to back).
-TM_DEV void attn_fwd_wave_il(const bf16* ks, const bf16* vt, const bf16x8 (&qf)[4], f32x16 (&o)[2], float& mx,
-                             float& sum, int lane) {
-  constexpr int KROW = Lay<bf16>::KROW;
-  const int r = lane & 31, h = lane >> 5;
-  f32x16 s[8];
-  float mk[8];
-#pragma unroll
-  for (int kt = 0; kt < 8; ++kt) {
-    s[kt] = (f32x16){};
-#pragma unroll
-    for (int st = 0; st < 4; ++st) mma16(s[kt], load8(ks + (kt * 32 + r) * KROW + st * 16 + 8 * h), qf[st]);
-    mk[kt] = tree_max16(s[kt]);
-  }
-  float m = fmaxf(fmaxf(fmaxf(mk[0], mk[1]), fmaxf(mk[2], mk[3])), fmaxf(fmaxf(mk[4], mk[5]), fmaxf(mk[6], mk[7])));
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  const float ml = m * LOG2E;
-  o[0] = (f32x16){};
-  o[1] = (f32x16){};
-  float lk[8];
-#pragma unroll
-  for (int kt = 0; kt < 8; ++kt) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) s[kt][i] = __builtin_amdgcn_exp2f(fmaf(s[kt][i], LOG2E, -ml));
-    lk[kt] = tree_sum16(s[kt]);
-#pragma unroll
-    for (int sp = 0; sp < 2; ++sp) {
-      const bf16x8 p = acc_as_operand<bf16>(s[kt], sp);
-#pragma unroll
-      for (int dt = 0; dt < 2; ++dt) mma16(o[dt], value_frag<bf16>(vt, dt, kt * 32 + 16 * sp, lane), p);
-    }
-  }
-  float l = ((lk[0] + lk[1]) + (lk[2] + lk[3])) + ((lk[4] + lk[5]) + (lk[6] + lk[7]));
-  l += __shfl_xor(l, 32, 64);
-  mx = m;
-  sum = l;
-}
-
-// attn_fwd_wave_il with its LDS fragments software-pipelined one tile ahead (one wave per SIMD
-// has no partner wave to hide a read's latency: the il form waited on every key / value read
-// right before its MFMA).  Key fragments of tile kt + 1 and value fragments of tile kt + 1 are
-// issued before the MFMAs of tile kt; the max tree of tile kt - 1 and the exp / pack of tile
-// kt + 1 run beside them.  Same arithmetic, same order of every sum: bitwise the il results
-// (scripts/dev/fwd_pipe_ab.py: 14.4 -> 13.8 us per call at the bench shape).
+// attn_fwd_wave with the per-tile work interleaved for the scheduler (the max tree of score tile
+// kt beside the MFMAs of tile kt + 1, the exp / sum / bf16 packing of tile kt beside its P.V
+// MFMAs) and its LDS fragments software-pipelined one tile ahead: one wave per SIMD has no
+// partner wave to hide a read's latency.  Key fragments of tile kt + 1 and value fragments of
+// tile kt + 1 are issued before the MFMAs of tile kt; the max tree of tile kt - 1 and the exp /
+// pack of tile kt + 1 run beside them.  Same arithmetic and order of every sum as the form with
+// just-in-time reads it replaced (bitwise equal; 14.4 -> 13.8 us per call at the bench shape).
 TM_DEV void attn_fwd_wave_pipe(const bf16* ks, const bf16* vt, const bf16x8 (&qf)[4], f32x16 (&o)[2], float& mx,
                                float& sum, int lane) {
   constexpr int KROW = Lay<bf16>::KROW;
@@ -751,8 +630,7 @@ TM_DEV void attn_fwd_wave_pipe(const bf16* ks, const bf16* vt, const bf16x8 (&qf
   sum = l;
 }
 
-template <int VAR = 0>  // ablation: 1 no conv MFMAs, 2 no attention phase, 3 prologue only, 9 stamps,
-                        // 6 the earlier attention form (attn_fwd_wave_il: reads just in time)
+template <bool STAMP = false>   // STAMP: per-wave s_memtime stamps (diagnostic build only)
 __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict__ q, const bf16* __restrict__ v,
                                                           const bf16* __restrict__ kl_t, const bf16* __restrict__ y_t,
                                                           const float* __restrict__ wconv, int n, int nh, int wpg,
@@ -774,7 +652,7 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
   const bf16* qb = q + (size_t)bh * n * DH;
   const bf16* vb = v + (size_t)bh * n * DH;
   const int ld = nh * DH;
-  a1p_stamp<VAR>(0, wave);
+  a1p_stamp<STAMP>(0, wave);
 
   // ---- prologue: keys, Y, taps and this wave's first query fragments through registers;
   //      the v window by LDS-DMA, left in flight through the first attention phase ----
@@ -818,12 +696,7 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();  // keys / Y / band table in LDS; the window DMA may still be in flight
-  a1p_stamp<VAR>(1, wave);
-  if constexpr (VAR == 3) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (c < c_end && lane == 0) lse1[(size_t)bh * n + c * 32] = to_f(ks[tid]) + to_f(vt[tid]) + to_f(qf[0][0]);
-    return;
-  }
+  a1p_stamp<STAMP>(1, wave);
 
   bool first = true;
   for (;;) {
@@ -831,16 +704,8 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
     const int t0 = c * 32;
     f32x16 o[2];
     float mx = 0.f, sum = 1.f;
-    if (active) {
-      if constexpr (VAR == 2) {
-        o[0] = (f32x16){}; o[1] = (f32x16){};
-        mx = to_f(qf[0][0]);
-      } else {
-        if constexpr (VAR == 6) attn_fwd_wave_il(ks, vt, qf, o, mx, sum, lane);
-        else attn_fwd_wave_pipe(ks, vt, qf, o, mx, sum, lane);
-      }
-    }
-    if (first) a1p_stamp<VAR>(2, wave);
+    if (active) attn_fwd_wave_pipe(ks, vt, qf, o, mx, sum, lane);
+    if (first) a1p_stamp<STAMP>(2, wave);
     const int cn = c + A1P_WAVES;
     if (cn < c_end) {
 #pragma unroll
@@ -852,7 +717,7 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       first = false;
-      a1p_stamp<VAR>(3, wave);
+      a1p_stamp<STAMP>(3, wave);
     }
     if (!active) break;
     // band fragments from the shared table.  At the sequence ends the window rows outside
@@ -868,14 +733,12 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int i = 0; i < 16; ++i) o[dt][i] *= inv;
-    if constexpr (VAR != 1) {
-      const bf16* wc = win + (size_t)(t0 - HALF - w0) * DH;
+    const bf16* wc = win + (size_t)(t0 - HALF - w0) * DH;
 #pragma unroll
-      for (int dt = 0; dt < 2; ++dt)
+    for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) mma16(o[dt], a1p_window_frag(wc, dt, 16 * s, lane), band[s]);
-    }
-    if (c == c_begin + wave) a1p_stamp<VAR>(4, wave);
+      for (int s = 0; s < 4; ++s) mma16(o[dt], a1p_window_frag(wc, dt, 16 * s, lane), band[s]);
+    if (c == c_begin + wave) a1p_stamp<STAMP>(4, wave);
     if (h == 0) lse1[(size_t)bh * n + t0 + r] = mx + __logf(sum);
     // O^T registers -> [32 q][72] bf16 wave stage -> full 128-B row stores, 16 B per lane
     // (row-per-lane 8-B stores are store-issue bound)
@@ -902,11 +765,11 @@ __global__ __launch_bounds__(256) void a1_fwd_bf16_kernel(const bf16* __restrict
       *(f32x4*)(dst + (size_t)(p >> 3) * ld + (p & 7) * 8) = ov[i];
     }
     wave_lds_fence();  // stage read back before the next chunk rewrites it
-    if (c == c_begin + wave) a1p_stamp<VAR>(5, wave);
+    if (c == c_begin + wave) a1p_stamp<STAMP>(5, wave);
     c = cn;
     if (c >= c_end) break;
   }
-  a1p_stamp<VAR>(6, wave);
+  a1p_stamp<STAMP>(6, wave);
 }
 
 // ---------------------------------------------------------------------------
@@ -991,7 +854,7 @@ __global__ __launch_bounds__(512) void a3_fwd_v2_kernel(const float* __restrict_
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int p = blockIdx.x, bh = blockIdx.y, nbh = gridDim.y;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
-  auto stamp = [&](int slot) { if (ST) a1p_stamp<ST ? 9 : 0>(slot, wave); };
+  auto stamp = [&](int slot) { if (ST) a1p_stamp<ST != 0>(slot, wave); };
   stamp(0);
   const int S32 = n / 32;
   const int sb0 = (int)((long long)p * S32 / P), sb1 = (int)((long long)(p + 1) * S32 / P);
@@ -1196,19 +1059,6 @@ __global__ __launch_bounds__(256) void a3_combine_kernel(const float* __restrict
   }
   *(f32x4*)(w + q0 * DH + d4) = acc / L;
   if (d4 == 0) lse3[q0] = M + __logf(L);
-}
-
-// ---------------------------------------------------------------------------
-// D3[bh][q] = dW[q] . W[q]; dW_t = T(dW).  grid (nbh*256/4), block 256 (one wave per row)
-template <typename T>
-__global__ void rowdot_cast_kernel(const float* __restrict__ dw, const float* __restrict__ w, float* __restrict__ dd,
-                                   T* __restrict__ dw_t, int rows) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= rows) return;
-  const float a = dw[(size_t)r * DH + lane];
-  const float s = wave_sum(a * w[(size_t)r * DH + lane]);
-  dw_t[(size_t)r * DH + lane] = from_f<T>(a);
-  if (lane == 0) dd[r] = s;
 }
 
 // T copy of an fp32 [rows][64] matrix
@@ -1579,10 +1429,15 @@ enum { MODE_A3 = 0, MODE_A1 = 1 };
 int tm_splitk_reduce_typed(const void* slab, int slab_dtype, float* out, int splits, long long count, float alpha,
                            int accumulate, tm_reduce_queue* q, void* stream);
 namespace {
+// Selectors of the diagnostic build (tm_debug_set_nys_sel; NYS_SEL in scripts/microbench.py): the
+// stamped instantiations of the shipped bf16 kernels (per-wave s_memtime into g_a1_stamps; the
+// _CHUNK forms stamp inside one query chunk instead of the phases).  The product compiles NYS_AUTO in.
+enum NysSel { NYS_AUTO = 0, NYS_STAMP_A1_FWD, NYS_STAMP_A3_FWD, NYS_STAMP_A1_BWD, NYS_STAMP_A1_BWD_CHUNK,
+              NYS_STAMP_A3_BWD, NYS_STAMP_A3_BWD_CHUNK };
 #ifdef TM_DIAG
-int g_nys_variant = 0;
+int g_nys_sel = NYS_AUTO;
 #endif
-#define NYS_VARIANT TM_DIAG_VAR(g_nys_variant)
+#define NYS_SEL TM_DIAG_VAR(g_nys_sel)
 
 template <typename T> struct BwdLay {
   static constexpr int QT_ROW = 32 + 4;              // Q^T / dO^T chunk [64 d][36]
@@ -1846,33 +1701,28 @@ TM_DEV bf16x8 frag_tr_rows(const bf16* S, int mb, int kb, int lane) {
 }
 TM_DEV bf16x8 frag_tr_acc(const bf16* S, int mb, int kb, int lane) { return frag_tr_rows<BwdLay16::QROW>(S, mb, kb, lane); }
 
-// DQ2 (default): dQ = dS K by two waves, one 32-column d tile each over ALL the workgroup's keys in
-// one accumulation chain (no cross-wave partials through LDS, no third barrier per chunk; the other
-// waves go on to the next chunk's S / dP / dV / dK meanwhile).  DQ2 = 0: the earlier form (every
-// wave a key group's partial, summed through LDS by the group-0 waves; diagnostic build only).
-template <int MODE, int NW = 8, int ST = 0, int DQ2 = 1>   // ST: diagnostic s_memtime stamps (g_a1_stamps): 1 phases, 2 one chunk
-                                                           // DQ2 = 2: the DQ2 chain with its reads just in time
+// dQ = dS K by two waves, one 32-column d tile each over ALL the workgroup's keys in one
+// accumulation chain (no cross-wave partials through LDS, no third barrier per chunk; the other
+// waves go on to the next chunk's S / dP / dV / dK meanwhile).
+template <int MODE, int NW = 8, int ST = 0>   // ST: diagnostic s_memtime stamps (g_a1_stamps): 1 phases, 2 one chunk
 __global__ __launch_bounds__(64 * NW) void attn_bwd_bf16_kernel(BwdArgs a) {
   using LY = std::conditional_t<NW == 9, BwdLay9, BwdLay16>;
   static_assert(NW == 8 || (NW == 9 && MODE == MODE_A3), "9-wave form: A3 even split only");
   constexpr int NT = 64 * NW;
   constexpr int KT_ROW = LY::KT_ROW, DS_ROW = LY::DS_ROW, QROW = LY::QROW;
-  // dQ roles: 2 d tiles x NKQ key groups of KQS 16-deep k-steps (8 waves: 4 x 64 keys; 9: 3 x 96)
-  constexpr int NKQ = NW == 9 ? 3 : 4, KQS = 2 * NW / NKQ;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16* kt_s = (bf16*)(smem + LY::KT_OFF);
   bf16* ds_s = (bf16*)(smem + LY::DS_OFF);
   bf16* qs = (bf16*)(smem + LY::QS_OFF);
   bf16* os = (bf16*)(smem + LY::OS_OFF);
-  float* xch = (float*)(smem + LY::XC_OFF);
   float* lse_s = (float*)(smem + LY::LS_OFF);
   float* dd_s = lse_s + LY::MAXQ;
   float* stage = (float*)smem;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
   const int blk = blockIdx.x, bh = blockIdx.y, nh = a.nh;
-  auto stamp = [&](int slot) { if (ST == 1 && wave < 8) a1p_stamp<ST ? 9 : 0>(slot, wave); };
-  auto cstamp = [&](int c0, int slot) { if (ST == 2 && c0 == 64 && wave < 8) a1p_stamp<ST ? 9 : 0>(slot, wave); };
+  auto stamp = [&](int slot) { if (ST == 1 && wave < 8) a1p_stamp<ST != 0>(slot, wave); };
+  auto cstamp = [&](int c0, int slot) { if (ST == 2 && c0 == 64 && wave < 8) a1p_stamp<ST != 0>(slot, wave); };
   stamp(0);
   int key0 = (MODE == MODE_A3) ? blk * NL : 0;
   int nunits = 8;  // 32-key units of this workgroup (wave w < nunits owns keys key0 + 32 w ..)
@@ -1957,8 +1807,6 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_bf16_kernel(BwdArgs a) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) { dvt[i] = (f32x16){}; dkt[i] = (f32x16){}; }
 
-  const int dt_q = wave & 1, kq = wave >> 1;  // dQ role: d tile, key group (waves < 2 NKQ)
-  const bool dq_role = wave < 2 * NKQ;
 #pragma unroll 1
   for (int c0 = 0; c0 < q_count; c0 += 32) {
     // S = Q K^T, dP = dO V^T: rows = queries (registers), cols = this wave's keys (lanes)
@@ -1994,44 +1842,36 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_bf16_kernel(BwdArgs a) {
       }
     }
     cstamp(c0, 1);
-    __syncthreads();  // previous chunk's dQ reads of ds_s / xch are done
+    __syncthreads();  // previous chunk's dQ reads of ds_s are done
     cstamp(c0, 2);
 #pragma unroll
     for (int i = 0; i < 16; ++i) ds_s[acc_row(i, h) * DS_ROW + mykey + r] = from_f<bf16>(dp[i]);  // 0: idle wave
     __syncthreads();
     cstamp(c0, 3);
-    if constexpr (DQ2) {
+    {
       // waves W0, W0 + 1 (SIMDs that do not host the 9-wave form's ninth wave): d tile wave - W0
       constexpr int W0 = NW == 9 ? 1 : 0;
       if (wave == W0 || wave == W0 + 1) {
         const int dtq = wave - W0;
         f32x16 acc = (f32x16){};
-        if constexpr (DQ2 == 1) {
-          // software-pipelined: the operand reads of k-steps st + 2, st + 3 are issued before the
-          // MFMAs of st, st + 1 (left to itself the compiler sinks each pair of reads to its MFMAs and
-          // waits on them: A1 backward 38.5 -> 37.7 us, A3 32.9 -> 32.6, bitwise the same)
-          constexpr int NS = 2 * NW;
-          const bf16* da = ds_s + r * DS_ROW + 8 * h;
-          const bf16* kb = kt_s + (dtq * 32 + r) * KT_ROW + 8 * h;
-          bf16x8 fa[4], fb[4];
+        // software-pipelined: the operand reads of k-steps st + 2, st + 3 are issued before the
+        // MFMAs of st, st + 1 (left to itself the compiler sinks each pair of reads to its MFMAs and
+        // waits on them: A1 backward 38.5 -> 37.7 us, A3 32.9 -> 32.6, bitwise the same)
+        constexpr int NS = 2 * NW;
+        const bf16* da = ds_s + r * DS_ROW + 8 * h;
+        const bf16* kb = kt_s + (dtq * 32 + r) * KT_ROW + 8 * h;
+        bf16x8 fa[4], fb[4];
 #pragma unroll
-          for (int st = 0; st < 2; ++st) { fa[st] = load8(da + st * 16); fb[st] = load8(kb + st * 16); }
+        for (int st = 0; st < 2; ++st) { fa[st] = load8(da + st * 16); fb[st] = load8(kb + st * 16); }
 #pragma unroll
-          for (int st = 0; st < NS; st += 2) {
+        for (int st = 0; st < NS; st += 2) {
 #pragma unroll
-            for (int u = 2; u < 4; ++u)
-              if (st + u < NS) { fa[(st + u) & 3] = load8(da + (st + u) * 16); fb[(st + u) & 3] = load8(kb + (st + u) * 16); }
-            __builtin_amdgcn_sched_barrier(0);
-            mma16(acc, fa[st & 3], fb[st & 3]);
-            if (st + 1 < NS) mma16(acc, fa[(st + 1) & 3], fb[(st + 1) & 3]);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-        } else {   // DQ2 == 2 (diagnostic build): the reads just in time
-#pragma unroll
-        for (int st = 0; st < 2 * NW; ++st) {
-          const int kk = st * 16 + 8 * h;
-          mma16(acc, load8(ds_s + r * DS_ROW + kk), load8(kt_s + (dtq * 32 + r) * KT_ROW + kk));
-        }
+          for (int u = 2; u < 4; ++u)
+            if (st + u < NS) { fa[(st + u) & 3] = load8(da + (st + u) * 16); fb[(st + u) & 3] = load8(kb + (st + u) * 16); }
+          __builtin_amdgcn_sched_barrier(0);
+          mma16(acc, fa[st & 3], fb[st & 3]);
+          if (st + 1 < NS) mma16(acc, fa[(st + 1) & 3], fb[(st + 1) & 3]);
+          __builtin_amdgcn_sched_barrier(0);
         }
         cstamp(c0, 4);
         if (MODE == MODE_A1 && a.dqkv) {
@@ -2051,63 +1891,6 @@ __global__ __launch_bounds__(64 * NW) void attn_bwd_bf16_kernel(BwdArgs a) {
         }
         cstamp(c0, 5);
       }
-    } else {
-    // dQ chunk [32 q x 64 d] = dS [32 x NK] . K [NK x 64]: this wave: d tile dt_q, keys 16 KQS kq ..
-      f32x16 acc = (f32x16){};
-      float* dst = MODE == MODE_A1 ? a.dq + bh * a.dq_bh : a.dq + (size_t)blk * a.slab_stride + bh * a.dq_bh;
-      dst += (size_t)(q_begin + c0) * DH;
-      if (dq_role) {
-#pragma unroll
-        for (int st = 0; st < KQS; ++st) {
-          const int kk = kq * 16 * KQS + st * 16 + 8 * h;
-          mma16(acc, load8(ds_s + r * DS_ROW + kk), load8(kt_s + (dt_q * 32 + r) * KT_ROW + kk));
-        }
-        // [32 q][64 d] partials of key group kq (9 waves: every group, 3 x 8 KB; 8 waves: groups 1-3)
-        if (NW == 9 || kq > 0) {
-          float* xs = xch + (NW == 9 ? kq : kq - 1) * 2048;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) xs[acc_row(i, h) * 64 + dt_q * 32 + r] = acc[i];
-        }
-      }
-      cstamp(c0, 4);
-      __syncthreads();
-      cstamp(c0, 5);
-      if constexpr (NW == 9) {
-        // every thread: one 4-column piece of the chunk's dq, the key groups summed in a fixed order
-        if (tid < 512) {
-          const int q = tid >> 4, d4 = (tid & 15) * 4;
-          const f32x4 v = (*(const f32x4*)(xch + q * 64 + d4) + *(const f32x4*)(xch + 2048 + q * 64 + d4)) +
-                          *(const f32x4*)(xch + 4096 + q * 64 + d4);
-          if (MODE == MODE_A3 && a.slab_bf16)
-            *(bf16x4*)((bf16*)a.dq + (size_t)blk * a.slab_stride + bh * a.dq_bh + (size_t)(q_begin + c0 + q) * DH + d4) =
-                (bf16x4){(bf16)v[0], (bf16)v[1], (bf16)v[2], (bf16)v[3]};
-          else
-            *(f32x4*)(dst + (size_t)q * DH + d4) = v;
-        }
-      } else if (kq == 0) {
-        if (MODE == MODE_A1 && a.dqkv) {
-          // bf16 q rows of dqkv (half the bytes of the fp32 rows; the landmark term is added in place
-          // by tm_nys_assemble_q_slab_inplace)
-          const int bag = bh / nh, hh = bh % nh, ld = 3 * nh * DH;
-          bf16* qo = (bf16*)a.dqkv + ((size_t)bag * a.q_total + q_begin + c0) * ld + hh * DH + dt_q * 32 + r;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            float v = acc[i];
-#pragma unroll
-            for (int g = 0; g < NKQ - 1; ++g) v += xch[g * 2048 + acc_row(i, h) * 64 + dt_q * 32 + r];
-            qo[(size_t)acc_row(i, h) * ld] = (bf16)(a.dq_scale * v);
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            float v = acc[i];
-#pragma unroll
-            for (int g = 0; g < NKQ - 1; ++g) v += xch[g * 2048 + acc_row(i, h) * 64 + dt_q * 32 + r];
-            dst[(size_t)acc_row(i, h) * DH + dt_q * 32 + r] = v;
-          }
-        }
-      }
-      cstamp(c0, 6);
     }
     if (c0 == 0) stamp(3);
     if (c0 == 96) stamp(4);
@@ -2256,30 +2039,6 @@ __global__ void assemble_dqkv_kernel(const float* __restrict__ dq, const float* 
   store8<T>(dqkv + ((size_t)bag * n + t) * (3 * inner) + c, out);
 }
 
-// q part of dqkv only (the k / v parts written by the fused A3 backward):
-// q = scale * (dq + (dql_a + dql_b)[t / l] / l); grid (ceil(n * nh * 8 / 256), nbags), block 256
-template <typename T>
-__global__ void assemble_q_kernel(const float* __restrict__ dq, int dq_row, const float* __restrict__ dql_a,
-                                  const float* __restrict__ dql_b, int n, int l, int nh, float scale,
-                                  T* __restrict__ dqkv) {
-  const int inner = nh * DH, per_row = inner / 8;
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (item >= (long long)n * per_row) return;
-  const int c = (int)(item % per_row) * 8;
-  const int t = (int)(item / per_row), bag = blockIdx.y;
-  const int head = c / DH, d = c % DH;
-  const size_t bh = (size_t)bag * nh + head;
-  const size_t row = (bh * n + t) * DH + d;
-  const size_t lrow = (bh * NL + t / l) * DH + d;
-  const float inv_l = 1.0f / (float)l;
-  const f32x8 a = (dq_row < 0 || t == dq_row) ? load8<float>(dq + row) : (f32x8){};  // dq_row: the only non-zero row
-  const f32x8 b0 = load8<float>(dql_a + lrow), b1 = load8<float>(dql_b + lrow);
-  vec8<T> out;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) out[e] = from_f<T>(scale * (a[e] + (b0[e] + b1[e]) * inv_l));
-  store8<T>(dqkv + ((size_t)bag * n + t) * (3 * inner) + c, out);
-}
-
 // q part of dqkv with the A3 backward's dq~ partial slab reduced in the same launch (no separate
 // split-K reduce, no dq~3 round trip): q = scale * (dq + (dql + sum_p slab[p])[t / l] / l).
 // grid (256 landmarks, nbags), block 512: the workgroup's first QP dq pieces per thread are
@@ -2375,8 +2134,8 @@ __global__ __launch_bounds__(AQ_THREADS) void assemble_q_slab_kernel(const float
 
 // ============================ C entry points ===============================
 #ifdef TM_DIAG
-extern "C" void tm_debug_set_nys_variant(int value) { g_nys_variant = value; }
-// copy the VAR 9 a1_fwd stamps ([block][wave][8] u64) to a host buffer (diagnostics only)
+extern "C" void tm_debug_set_nys_sel(int sel) { g_nys_sel = sel; }   // a NysSel
+// copy the stamped kernels' stamps ([block][wave][8] u64) to a host buffer (diagnostics only)
 extern "C" int tm_debug_a1_stamps(unsigned long long* host, int count) {
   TM_REQUIRE(count > 0 && count <= 512 * 8 * 8, "a1_stamps: bad count");
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_a1_stamps), count * sizeof(unsigned long long)) != hipSuccess) {
@@ -2411,12 +2170,7 @@ extern "C" int tm_nys_sim2_softmax(const float* ql, const float* kl, int nbh, fl
 extern "C" int tm_nys_sim2_softmax_split(const float* ql, const float* kl, int nbh, float* a2, void* a2s,
                                          void* stream) {
   TM_REQUIRE(a2s, "sim2_softmax_split: a2s is required");
-#ifdef TM_DIAG
-  if (NYS_VARIANT == 21)   // the MFMA form (measured slower: 15.1 vs 12 us with 64 workgroups)
-    sim2_softmax_mfma_kernel<<<dim3(nbh, NL / 32), 512, 0, (hipStream_t)stream>>>(ql, kl, a2, (bf16*)a2s);
-  else
-#endif
-    sim2_softmax_kernel<<<dim3(nbh, NL / S2_ROWS), 256, 0, (hipStream_t)stream>>>(ql, kl, a2, (bf16*)a2s);
+  sim2_softmax_kernel<<<dim3(nbh, NL / S2_ROWS), 256, 0, (hipStream_t)stream>>>(ql, kl, a2, (bf16*)a2s);
   TM_CHECK_LAUNCH();
   return 0;
 }
@@ -2447,12 +2201,12 @@ void launch_a3_fwd_v2(const float* ql, const void* k, const void* v, int nbh, in
   const bf16* kb = (const bf16*)k;
   const bf16* vb = (const bf16*)v;
 #ifdef TM_DIAG
-  if (NYS_VARIANT == 32 && !s2.a2) {   // diagnostic: s_memtime stamps per wave (tm_debug_a1_stamps)
+  if (NYS_SEL == NYS_STAMP_A3_FWD && !s2.a2) {   // s_memtime stamps per wave (tm_debug_a1_stamps)
     tm_allow_smem(a3_fwd_v2_kernel<1>, A3V_BYTES);
     a3_fwd_v2_kernel<1><<<grid, 512, A3V_BYTES, st>>>(ql, kb, vb, n, P, po, pm, pl, s2);
     return;
   }
-  if (NYS_VARIANT == 32 && s2.a2 && P * 8 == NL) {   // the same with the fused A2 rows
+  if (NYS_SEL == NYS_STAMP_A3_FWD && s2.a2 && P * 8 == NL) {   // the same with the fused A2 rows
     tm_allow_smem(a3_fwd_v2_kernel<1, 4>, A3V_BYTES);
     a3_fwd_v2_kernel<1, 4><<<grid, 512, A3V_BYTES, st>>>(ql, kb, vb, n, P, po, pm, pl, s2);
     return;
@@ -2518,17 +2272,13 @@ extern "C" int tm_nys_a1_fwd(int dtype, const void* q, const void* v, const void
                              const float* wconv, int nbh, int nh, int n, void* merged, float* lse1, void* stream) {
   TM_REQUIRE(n > 0 && n % NL == 0 && nbh % nh == 0, "a1_fwd: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TM_BF16 && NYS_VARIANT != 14) {
+  if (dtype == TM_BF16) {
     const int cph = n / 32;
     int wpg = std::max(1, std::min(tm_cu_count() / std::max(nbh, 1), cph));
     wpg = std::max(wpg, (cph + A1P_MAXCH - 1) / A1P_MAXCH);  // <= A1P_MAXCH chunks per workgroup
+    auto kern = a1_fwd_bf16_kernel<false>;
 #ifdef TM_DIAG
-    // ablation variants 11-19 (microbench only): 10 + VAR
-    auto kern = NYS_VARIANT == 11 ? a1_fwd_bf16_kernel<1> : NYS_VARIANT == 12 ? a1_fwd_bf16_kernel<2>
-              : NYS_VARIANT == 13 ? a1_fwd_bf16_kernel<3> : NYS_VARIANT == 19 ? a1_fwd_bf16_kernel<9>
-              : NYS_VARIANT == 16 ? a1_fwd_bf16_kernel<6> : a1_fwd_bf16_kernel<0>;
-#else
-    auto kern = a1_fwd_bf16_kernel<0>;
+    if (NYS_SEL == NYS_STAMP_A1_FWD) kern = a1_fwd_bf16_kernel<true>;
 #endif
     tm_allow_smem(kern, A1P_BYTES);
     kern<<<dim3(wpg, nbh), 256, A1P_BYTES, st>>>((const bf16*)q, (const bf16*)v, (const bf16*)kl_t,
@@ -2540,23 +2290,10 @@ extern "C" int tm_nys_a1_fwd(int dtype, const void* q, const void* v, const void
   TM_DTYPE_DISPATCH(dtype, ({
     const size_t sm1 = ((size_t)NL * Lay<T>::KROW + Lay<T>::VELEMS) * sizeof(T);
     const size_t sm = sm1 > A1_EPI_BYTES ? sm1 : A1_EPI_BYTES;
-#ifdef TM_DIAG
-    auto kern = NYS_VARIANT == 1 ? a1_fwd_kernel<T, 1> : NYS_VARIANT == 2 ? a1_fwd_kernel<T, 2> : a1_fwd_kernel<T, 0>;
-#else
-    auto kern = a1_fwd_kernel<T, 0>;
-#endif
-    tm_allow_smem(kern, sm);
-    kern<<<dim3(n / 128, nbh), 256, sm, st>>>((const T*)q, (const T*)v, (const T*)kl_t,
+    tm_allow_smem(a1_fwd_kernel<T>, sm);
+    a1_fwd_kernel<T><<<dim3(n / 128, nbh), 256, sm, st>>>((const T*)q, (const T*)v, (const T*)kl_t,
                                               (const T*)y_t, wconv, n, nh, (T*)merged, lse1);
   }));
-  TM_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int tm_nys_rowdot_cast(int dtype, const float* dw, const float* w, int rows, float* dd, void* dw_t,
-                                  void* stream) {
-  TM_DTYPE_DISPATCH(dtype, (rowdot_cast_kernel<T><<<(rows + 3) / 4, 256, 0, (hipStream_t)stream>>>(
-                               dw, w, dd, (T*)dw_t, rows)));
   TM_CHECK_LAUNCH();
   return 0;
 }
@@ -2581,7 +2318,7 @@ extern "C" int tm_nys_conv_bwd(int dtype, const void* dmerged, const void* merge
                                tm_reduce_queue* rq, void* stream) {
   TM_REQUIRE(nbh % nh == 0 && n > 0, "conv_bwd: bad shape");
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TM_BF16 && NYS_VARIANT != 7) {
+  if (dtype == TM_BF16) {
     const int r = conv_bwd_rows(nbh, n), nblk = (n + r - 1) / r;
     tm_allow_smem(conv_bwd_mfma_kernel, CbLay::BYTES);
     conv_bwd_mfma_kernel<<<dim3(nblk, nbh), 512, CbLay::BYTES, st>>>(
@@ -2642,7 +2379,7 @@ int a1_bwd_impl(int dtype, const void* q, const void* dmerged, const void* kl_t,
                 const float* d1, int nbh, int nh, int n, int queries_per_wg, float* dq, void* dqkv, float dq_scale,
                 float* work, float* dkl, float* dy, int accumulate, tm_reduce_queue* rq, void* stream) {
   TM_REQUIRE(queries_per_wg % 32 == 0 && n % queries_per_wg == 0, "a1_bwd: queries_per_wg must divide n, x32");
-  const bool split = dtype == TM_BF16 && queries_per_wg <= NL && NYS_VARIANT != 3;
+  const bool split = dtype == TM_BF16 && queries_per_wg <= NL;
   TM_REQUIRE(!dqkv || split, "a1_bwd_dqkv: the bf16 split kernel only");
   const int nqc = split ? a1_bwd_split(nbh, n) : n / queries_per_wg;
   BwdArgs a{};
@@ -2662,25 +2399,14 @@ int a1_bwd_impl(int dtype, const void* q, const void* dmerged, const void* kl_t,
   hipStream_t st = (hipStream_t)stream;
   if (split) {
     a.q_total = n;
-    // the dk~ / dY partials as bf16 (diagnostic variant 37: fp32, the earlier form)
-    a.slab_bf16 = NYS_VARIANT != 37;
+    a.slab_bf16 = 1;   // the dk~ / dY partials as bf16
+    auto kern = attn_bwd_bf16_kernel<MODE_A1>;
 #ifdef TM_DIAG
-    if (NYS_VARIANT == 33 || NYS_VARIANT == 34) {   // diagnostic: stamps per wave (33 phases, 34 inside chunk 2)
-      auto kern = NYS_VARIANT == 33 ? attn_bwd_bf16_kernel<MODE_A1, 8, 1> : attn_bwd_bf16_kernel<MODE_A1, 8, 2>;
-      tm_allow_smem(kern, BwdLay16::BYTES);
-      kern<<<dim3(nqc, nbh), 512, BwdLay16::BYTES, st>>>(a);
-    } else if (NYS_VARIANT == 35) {   // diagnostic: the earlier cross-wave dQ form
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A1, 8, 0, 0>, BwdLay16::BYTES);
-      attn_bwd_bf16_kernel<MODE_A1, 8, 0, 0><<<dim3(nqc, nbh), 512, BwdLay16::BYTES, st>>>(a);
-    } else if (NYS_VARIANT == 36) {   // diagnostic: the dQ chain with its reads just in time
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A1, 8, 0, 2>, BwdLay16::BYTES);
-      attn_bwd_bf16_kernel<MODE_A1, 8, 0, 2><<<dim3(nqc, nbh), 512, BwdLay16::BYTES, st>>>(a);
-    } else
+    if (NYS_SEL == NYS_STAMP_A1_BWD) kern = attn_bwd_bf16_kernel<MODE_A1, 8, 1>;
+    if (NYS_SEL == NYS_STAMP_A1_BWD_CHUNK) kern = attn_bwd_bf16_kernel<MODE_A1, 8, 2>;
 #endif
-    {
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A1>, BwdLay16::BYTES);
-      attn_bwd_bf16_kernel<MODE_A1><<<dim3(nqc, nbh), 512, BwdLay16::BYTES, st>>>(a);
-    }
+    tm_allow_smem(kern, BwdLay16::BYTES);
+    kern<<<dim3(nqc, nbh), 512, BwdLay16::BYTES, st>>>(a);
   } else {
     TM_DTYPE_DISPATCH(dtype, (tm_allow_smem(attn_bwd_kernel<T, MODE_A1>, bwd_smem_bytes<T>()),
                               attn_bwd_kernel<T, MODE_A1><<<dim3(nqc, nbh), 512, bwd_smem_bytes<T>(), st>>>(a)));
@@ -2715,30 +2441,13 @@ void launch_a3_bwd_bf16(BwdArgs& a, int nbh, int n, hipStream_t st, int& slabs) 
   a.q_total = n;  // even split on
   slabs = sp.wpg;
   if (sp.nw == 9) {
+    auto kern = attn_bwd_bf16_kernel<MODE_A3, 9>;
 #ifdef TM_DIAG
-    if (NYS_VARIANT == 30) {   // diagnostic: s_memtime stamps per wave (tm_debug_a1_stamps)
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 9, 1>, BwdLay9::BYTES);
-      attn_bwd_bf16_kernel<MODE_A3, 9, 1><<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
-      return;
-    }
-    if (NYS_VARIANT == 31) {   // diagnostic: stamps inside query chunk 2
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 9, 2>, BwdLay9::BYTES);
-      attn_bwd_bf16_kernel<MODE_A3, 9, 2><<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
-      return;
-    }
-    if (NYS_VARIANT == 35) {   // diagnostic: the earlier cross-wave dQ form
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 9, 0, 0>, BwdLay9::BYTES);
-      attn_bwd_bf16_kernel<MODE_A3, 9, 0, 0><<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
-      return;
-    }
-    if (NYS_VARIANT == 36) {   // diagnostic: the dQ chain with its reads just in time
-      tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 9, 0, 2>, BwdLay9::BYTES);
-      attn_bwd_bf16_kernel<MODE_A3, 9, 0, 2><<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
-      return;
-    }
+    if (NYS_SEL == NYS_STAMP_A3_BWD) kern = attn_bwd_bf16_kernel<MODE_A3, 9, 1>;
+    if (NYS_SEL == NYS_STAMP_A3_BWD_CHUNK) kern = attn_bwd_bf16_kernel<MODE_A3, 9, 2>;
 #endif
-    tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 9>, BwdLay9::BYTES);
-    attn_bwd_bf16_kernel<MODE_A3, 9><<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
+    tm_allow_smem(kern, BwdLay9::BYTES);
+    kern<<<dim3(sp.wpg, nbh), 576, BwdLay9::BYTES, st>>>(a);
   } else {
     tm_allow_smem(attn_bwd_bf16_kernel<MODE_A3, 8>, BwdLay16::BYTES);
     attn_bwd_bf16_kernel<MODE_A3, 8><<<dim3(sp.wpg, nbh), 512, BwdLay16::BYTES, st>>>(a);
@@ -2769,7 +2478,7 @@ extern "C" int tm_nys_a3_bwd(int dtype, const void* ql_t, const void* dw_t, cons
   a.nh = nh; a.n_queries_per_wg = NL; a.n_key_rows = n;
   hipStream_t st = (hipStream_t)stream;
   int slabs = nkb;
-  if (dtype == TM_BF16 && NYS_VARIANT != 3) {
+  if (dtype == TM_BF16) {
     launch_a3_bwd_bf16(a, nbh, n, st, slabs);
   } else {
     TM_DTYPE_DISPATCH(dtype, (tm_allow_smem(attn_bwd_kernel<T, MODE_A3>, bwd_smem_bytes<T>()),
@@ -2829,17 +2538,6 @@ extern "C" int tm_nys_assemble_q_slab_inplace(const float* dql, const void* slab
   TM_REQUIRE(dql && slab && dqkv && ((uintptr_t)dqkv % 16) == 0, "assemble_q_slab_inplace: null / misaligned operand");
   assemble_q_slab_kernel<bf16, true><<<dim3(NL, nbags), AQ_THREADS, 0, (hipStream_t)stream>>>(
       nullptr, -1, dql, (const bf16*)slab, slabs, (long long)nbags * nh * NL * DH, n, n / NL, nh, scale, (bf16*)dqkv);
-  TM_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int tm_nys_assemble_q(int dtype, const float* dq, int dq_row, const float* dql_a, const float* dql_b,
-                                 int nbags, int nh, int n, float scale, void* dqkv, void* stream) {
-  TM_REQUIRE(n % NL == 0, "assemble_q: n must be a multiple of 256");
-  const long long items = (long long)n * nh * DH / 8;
-  TM_DTYPE_DISPATCH(dtype, (assemble_q_kernel<T><<<dim3((unsigned)((items + 255) / 256), nbags), 256, 0,
-                                                    (hipStream_t)stream>>>(dq, dq_row, dql_a, dql_b, n, n / NL, nh,
-                                                                           scale, (T*)dqkv)));
   TM_CHECK_LAUNCH();
   return 0;
 }

@@ -434,7 +434,7 @@ void add_term(tm_bmm_job& j, const float* A, int ta, const float* B, int tb) {
 }  // namespace
 
 #ifdef TM_DIAG
-// Debug/ablation switch for microbenchmarks only (not part of the supported ABI surface).
+// Dispatch-placement probe for microbenchmarks only (not part of the supported ABI surface).
 __global__ void xcc_map_kernel(int* out) {
   if (threadIdx.x == 0) out[blockIdx.x] = __builtin_amdgcn_s_getreg((3 << 11) | 20);  // HW_REG_XCC_ID[3:0]
 }
@@ -445,13 +445,6 @@ extern "C" int tm_debug_xcc_map(int* out, int nblocks, int threads, void* stream
   xcc_map_kernel<<<nblocks, threads, 0, (hipStream_t)stream>>>(out);
   TM_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" void tm_debug_set_nys_variant(int value);
-extern "C" void tm_debug_set_gemm_variant(int value);
-extern "C" void tm_debug_set_variant(int which, int value) {
-  if (which == 1) tm_debug_set_nys_variant(value);
-  if (which == 2) tm_debug_set_gemm_variant(value);
 }
 #endif
 

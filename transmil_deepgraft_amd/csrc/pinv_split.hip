@@ -48,12 +48,6 @@ constexpr int EPI_LDS = 64 * EROW * 4;  // the fp32 output tile (17 KB); one wor
 constexpr int MAXJ = 3;
 constexpr int NPROD = 8;                // producer (LDS-DMA) waves; 4 consumer waves
 constexpr int NTHREADS = 64 * (4 + NPROD);
-// persistent chain kernel (pinv_team_kernel): per XCD a ticket and a done counter on their own
-// 64-B lines, then one error word; a forward and a backward set live at the end of `saved`
-constexpr int TEAM_XCD = 8;
-constexpr int TEAM_STRIDE = 16;                          // u32 words between two XCDs' counters
-constexpr int TEAM_SET_WORDS = TEAM_XCD * TEAM_STRIDE + 16;
-constexpr int TEAM_CTR_WORDS = 2 * TEAM_SET_WORDS;
 
 typedef __attribute__((address_space(3))) void lds_t;
 typedef __attribute__((address_space(1))) void glb_t;
@@ -94,21 +88,17 @@ struct SLaunch {
   const float* X;           // fp32 X (abs-sum jobs)
   float* sums;              // [2][nbh][256] row / column sums (abs-sum jobs)
   float* maxima_out;        // [2][nbh] (abs-sum jobs)
-  unsigned* zero_ctr;       // abs-sum launch: the team kernels' counters to zero (TEAM_CTR_WORDS), or null
   A3Combine a3;             // a3.w non-null: the row blockIdx.y == njobs runs the A3 forward's partial
                             // combine (a3_combine.h) on the CUs the chain's tiles leave idle
-  int dbg;                  // ablation (microbench only): 1 no DMA, 2 no LDS reads / MFMA, 3 no epilogue,
-                            // 4 epilogue only, 5 empty
-  unsigned long long* stamps;  // diagnostic build only: per-wave s_memtime stamps, or null
+#ifdef TM_DIAG
+  unsigned long long* stamps;  // per-wave s_memtime stamps of the product workgroups, or null
+#endif
 };
 
 #ifdef TM_DIAG
-int g_split_dbg = 0;
-unsigned long long* g_split_stamps = nullptr;
-#define SPLIT_DBG (dbg_)
+unsigned long long* g_split_stamps = nullptr;   // tm_debug_set_split_stamps
 #define SPLIT_STAMPS (stamp_out != nullptr)
 #else
-#define SPLIT_DBG 0
 #define SPLIT_STAMPS false
 #endif
 
@@ -293,19 +283,14 @@ TM_DEV void abssums(const SLaunch& L, int head, int which, float* red) {
 // 1 A lo, 2 B hi, 3 B lo).  One s_barrier per chunk: a chunk is read after the barrier that
 // follows its producers' counted vmcnt wait, and its slot is refilled after the barrier that
 // follows the consumers' last read of it.
-// TEAM: the tile runs inside the persistent chain kernel (pinv_team_kernel): every operand it
-// reads was written by another workgroup of the same XCD in this launch, so the LDS-DMA reads
-// bypass the CU's L1 (sc1, served by the XCD's L2) and so do the epilogue operand loads (nt).
-template <bool TEAM, int TEAM_POL = 16, bool DOT = false>
+template <bool DOT = false>
 TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* maxima, int head, int tile,
-                       char* smem, unsigned long long* stamp_out, int dbg_, bool dj = false) {
-  constexpr int DMA_POL = TEAM ? TEAM_POL : 0;   // cache policy of the LDS-DMA: sc1 in the team kernel
+                       char* smem, unsigned long long* stamp_out, bool dj = false) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m0 = (tile >> 2) * 64, n0 = (tile & 3) * 64;
   const size_t hoff = (size_t)head * MAT;
   const int nch = J.nterms * 4;
-  const int nchl = SPLIT_DBG == 4 ? 0 : nch;
   const bool st_on = SPLIT_STAMPS;
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (st_on) { ts[0] = rstamp(); ts[1] = stamp(); }
@@ -318,10 +303,7 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
   const void* e2p = J.e2;
   const int e1f = J.e1_f32, e2f = J.e2_f32;
   f32x4 e1raw[2], e2raw[2];
-  auto ld4 = [&](const f32x4* a) {
-    if constexpr (TEAM) return __builtin_nontemporal_load(a);   // L1 bypass (written in this launch)
-    else return *a;
-  };
+  auto ld4 = [&](const f32x4* a) { return *a; };
   auto eload = [&](const void* e, int f32, f32x4 (&r)[2]) {
     if (f32) {
       const float* q = (const float*)e;
@@ -374,17 +356,15 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
 #pragma unroll
       for (int i = 0; i < PPW; ++i)
         __builtin_amdgcn_global_load_lds((glb_t*)(base + (kr ? loff[1][i] : loff[0][i])), (lds_t*)(img + i * 1024),
-                                         16, 0, DMA_POL);
+                                         16, 0, 0);
     };
-    if (SPLIT_DBG != 1) {
-      issue(0);
-      issue(1);  // nch >= 4
-    }
-    for (int c = 0; c < nchl; ++c) {
+    issue(0);
+    issue(1);  // nch >= 4
+    for (int c = 0; c < nch; ++c) {
       if (c + 1 < nch) wait_vm<PPW>(); else wait_vm<0>();
       __builtin_amdgcn_s_barrier();  // chunk c landed (every producer); slot (c+2)%3 read by every consumer
       asm volatile("" ::: "memory");
-      if (c + 2 < nch && SPLIT_DBG != 1) issue(c + 2);
+      if (c + 2 < nch) issue(c + 2);
     }
   } else {  // ---------------------------------------------------------------- consumer
     const int wm = wv >> 1, wn = wv & 1;
@@ -399,11 +379,10 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
     const unsigned akr = lbase + kr_addr(wm * 32, lane), bkr = lbase + kr_addr(wn * 32, lane);
     f32x16 acc = (f32x16){};
     if (st_on) ts[2] = stamp();
-    for (int c = 0; c < nchl; ++c) {
+    for (int c = 0; c < nch; ++c) {
       __builtin_amdgcn_s_barrier();  // chunk c landed; every consumer is done with chunk c-1
       asm volatile("" ::: "memory");
       if (st_on && c == 0) ts[3] = stamp();
-      if (SPLIT_DBG == 2) continue;
       const unsigned sb = (c % NSLOT) * SLOT;
       switch ((c >> 2) ? code1 : code0) {
         case 0: chunk_mma<0, 0>(acc, sb, akr, bkr, akc, bkc); break;
@@ -420,8 +399,8 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
   }
   __syncthreads();  // the tile is in `ep`; every wave (producers too) takes one 8-element row piece
   __shared__ float dred[8];   // DOT: the 8 epilogue waves' partial dots
-  if (SPLIT_DBG == 3 || !epi) {
-    if (dotj && SPLIT_DBG != 3) __syncthreads();   // the one barrier the epilogue waves' dot sum takes
+  if (!epi) {
+    if (dotj) __syncthreads();   // the one barrier the epilogue waves' dot sum takes
     return;
   }
   const float diag = J.diag, e1s = J.e1s, e2s = J.e2s;
@@ -459,9 +438,8 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
     for (int e = 0; e < 8; ++e) v[e] = s[e] + e1s * e1v[e] + e2s * e2v[e];
     if (dg) v[row - col] += diag;
     // write-through outputs: the launch-end L2 write-back would otherwise hold the next level's start
-    // (forward chain 91.4 -> 85.5 us, backward 170.8 -> 169.1 us in graph replay; diagnostic variant 6
-    // = plain stores for the A/B, scripts/dev/pinv_graph_stamps.py --ab 0,6)
-    const bool wt = SPLIT_DBG != 6;
+    // (forward chain 91.4 -> 85.5 us, backward 170.8 -> 169.1 us in graph replay against plain stores)
+    const bool wt = true;
     if (J.c_f32) store_f8((float*)J.c, eoff, v, wt); else store_split8((bf16*)J.c, plane, eoff, v, wt);
     if (!dotj && J.cf) store_f8(J.cf, eoff, v, wt);
     if (J.c2) {
@@ -527,14 +505,13 @@ __global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
   const int head = u % nbh, tile = u / nbh;
   if (J.kind == KIND_ABSSUMS) {
     if (u < 2 * nbh) abssums(L, head, tile, (float*)smem);
-    if (L.zero_ctr && u == 0 && threadIdx.x < TEAM_CTR_WORDS) L.zero_ctr[threadIdx.x] = 0u;
     return;
   }
-  const int dbg_ = L.dbg;
-  if (SPLIT_DBG == 5) return;
-  unsigned long long* so = L.stamps ? L.stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 * 8 : nullptr;
-  stage_tile<false, 16, DOT>(J, nbh, L.plane, L.maxima, head, tile, smem, so, dbg_,
-                             DOT && (int)blockIdx.y == L.njobs - 1);
+  unsigned long long* so = nullptr;
+#ifdef TM_DIAG
+  if (L.stamps) so = L.stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 * 8;
+#endif
+  stage_tile<DOT>(J, nbh, L.plane, L.maxima, head, tile, smem, so, DOT && (int)blockIdx.y == L.njobs - 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -649,8 +626,7 @@ __global__ __launch_bounds__(256) void pinv_apply_bwd_kernel(const float* __rest
 }
 
 // ---------------------------------------------------------------------------
-// The chain as levels of independent jobs (shared by the host launch path and the device-side
-// persistent kernel, so both run the same products).
+// The chain as levels of independent jobs.
 #define TM_HD __host__ __device__ inline
 
 TM_HD SOp op(const void* p, int kr) { return SOp{(const bf16*)p, kr, 0}; }
@@ -678,11 +654,6 @@ struct FwdLayout {
   TM_HD bf16* scratch(int i) const { return (bf16*)(base + (long long)(4 * iters + 1 + i) * mat); }
   TM_HD float* sums() const { return base + (long long)(4 * iters + 3) * mat; }
   TM_HD float* maxima(int nbh) const { return sums() + 2LL * nbh * NL; }
-  // the persistent kernel's counters (forward set 0, backward set 1), 64-B aligned after the maxima
-  TM_HD unsigned* team_ctr(int nbh, int set) const {
-    const uintptr_t e = (uintptr_t)(maxima(nbh) + 2 * nbh);
-    return (unsigned*)((e + 63) & ~(uintptr_t)63) + set * TEAM_SET_WORDS;
-  }
 };
 
 TM_HD FwdLayout fwd_layout(float* saved, int nbh, int iters) {
@@ -798,119 +769,6 @@ TM_HD SJob bwd_level_job(const ChainArgs& a, int lvl, int jn) {
   }
 }
 
-#ifdef TM_DIAG
-// ---------------------------------------------------------------------------
-// Persistent chain kernel: every level of the forward (after L1) or of the backward in ONE
-// launch, instead of one launch per level (each launch boundary + ramp + first operand fetch
-// from beyond L2 costs ~3-4 us of the ~6.5 us a level took).
-//
-// Teams by XCD: a workgroup reads its XCD (HW_REG_XCC_ID) and works only on the heads
-// h = xcd (mod 8).  Every matrix of a head is then written and read by workgroups of ONE XCD
-// within this launch, so the hand-off stays in that XCD's L2 (the L2 is the coherence point of
-// its CUs): producers store plainly and drain (s_waitcnt vmcnt(0), barrier) before one
-// device-scope atomic add on the team's done counter; consumers poll it with L1-bypassing loads
-// and read every operand with L1-bypassing loads (LDS-DMA sc1, epilogue operands nt), so no
-// stale L1 line is ever used and no L2 write-back / invalidate is needed between levels.  The
-// operands written before this launch (X, the per-head maxima) come through the launch boundary.
-//
-// Work queue per team: a ticket counter hands out the team's tile-jobs in level order (level l
-// has njobs(l) x 16 tiles x its heads); a workgroup waits, before its tile-job, until the done
-// counter covers every tile-job of the earlier levels.  A ticket is only ever held by a running
-// workgroup and waits only on lower tickets, so the queue cannot deadlock whatever subset of the
-// grid is resident (another stream's kernels may hold CUs); every workgroup leaves once a
-// ticket is past the last level, and the last one to leave zeroes the counters for the next call.
-// A wait is bounded (~1 s): on expiry the error word is set and the workgroup leaves.
-//
-// Measured and rejected (diagnostic build only, variant 8): correct (test_pinv_split_gpu), but a
-// level still takes ~6 us -- a tile is bound by its own operand fill (128 KB per term into one
-// CU's LDS at ~31 B/clk: ~2 us, plus ~1.2 us to the first chunk and ~0.7 us of epilogue), and the
-// counter hand-off between levels costs ~1.1 us, the same as a launch boundary in graph replay.
-// Whole step in graph replay: 734 vs 758 slides/s with one launch per level
-// (scripts/dev/team_stamps.py, scripts/dev/ab_split_variant.py).
-struct TeamArgs {
-  ChainArgs c;
-  int dir;             // 0: forward levels, 1: backward levels
-  long long plane;
-  const float* maxima;
-  unsigned* ctr;       // TEAM_SET_WORDS: per XCD [ticket, .., done @ +16], then the exit count and error word
-  unsigned long long* stamps;   // diagnostic build: per ticket 40 u64 (stage stamps, then claim / ready / done / xcc / level)
-};
-
-constexpr int TEAM_GRID = 256;   // one workgroup per CU (113 KB of LDS each)
-// diagnostic stamps: ticket t of XCD x at record x * 512 + t
-TM_DEV unsigned t_global_base(int x, unsigned t) { return (unsigned)x * 512u + t; }
-
-template <int POL>
-__global__ __launch_bounds__(NTHREADS) void pinv_team_kernel(TeamArgs T) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  volatile unsigned* bc = (volatile unsigned*)(smem + STAGE_LDS + EPI_LDS);
-  const int tid = threadIdx.x;
-  const int x = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7;   // HW_REG_XCC_ID
-  const int nbh = T.c.nbh, iters = T.c.iters;
-  const int nh = nbh > x ? (nbh - 1 - x) / TEAM_XCD + 1 : 0;       // heads x, x + 8, ... of this team
-  unsigned* ticket = T.ctr + x * TEAM_STRIDE;
-  unsigned* done = ticket + TEAM_STRIDE / 2;
-  unsigned* exits = T.ctr + TEAM_XCD * TEAM_STRIDE;
-  unsigned* err = exits + 1;
-  const int nlev = T.dir == 0 ? fwd_levels(iters) : bwd_levels(iters);
-  const unsigned per_job = 16u * (unsigned)nh;
-  unsigned prefix = 0;   // tile-jobs of the levels before `lev`
-  int lev = 0;
-  while (nh > 0) {
-#ifdef TM_DIAG
-    const unsigned long long t_claim = T.stamps ? rstamp() : 0;
-#endif
-    if (tid == 0) bc[0] = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const unsigned t = __builtin_amdgcn_readfirstlane(bc[0]);
-    while (lev < nlev) {
-      const unsigned cnt = per_job * (T.dir == 0 ? fwd_level_njobs(iters, lev) : bwd_level_njobs(iters, lev));
-      if (t < prefix + cnt) break;
-      prefix += cnt;
-      ++lev;
-    }
-    if (lev >= nlev) break;
-    if (tid == 0) {   // every tile-job of the earlier levels done (relaxed L1-bypassing polls, bounded)
-      unsigned polls = 0;
-      while (__hip_atomic_load(done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < prefix) {
-        __builtin_amdgcn_s_sleep(2);
-        if (++polls > (1u << 24)) { __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); break; }
-      }
-    }
-    __syncthreads();   // also: every wave has read bc[0]
-    const unsigned r = t - prefix;
-    const int jn = (int)(r / per_job), rem = (int)(r % per_job);
-    const int head = x + TEAM_XCD * (rem >> 4), tile = rem & 15;
-    const SJob J = T.dir == 0 ? fwd_level_job(T.c, lev, jn) : bwd_level_job(T.c, lev, jn);
-    unsigned long long* so = nullptr;
-#ifdef TM_DIAG
-    const unsigned long long t_ready = T.stamps ? rstamp() : 0;
-    if (T.stamps) so = T.stamps + (size_t)t_global_base(x, t) * 40;
-#endif
-    stage_tile<true, POL, true>(J, nbh, T.plane, T.maxima, head, tile, smem, so, 0,
-                                T.dir == 1 && lev == nlev - 1 && jn == 1 && T.c.X != nullptr);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's tile stores have reached the L2
-    __syncthreads();
-    if (tid == 0) __hip_atomic_fetch_add(done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#ifdef TM_DIAG
-    if (so && tid == 0) {
-      so[32] = t_claim; so[33] = t_ready; so[34] = rstamp(); so[35] = x; so[36] = lev; so[37] = jn; so[38] = tile;
-    }
-#endif
-  }
-  if (tid == 0) {
-    const unsigned e = __hip_atomic_fetch_add(exits, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (e == gridDim.x - 1) {   // the last workgroup out: nothing of this launch touches the counters any more
-      for (int i = 0; i < TEAM_XCD; ++i) {
-        __hip_atomic_store(T.ctr + i * TEAM_STRIDE, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(T.ctr + i * TEAM_STRIDE + TEAM_STRIDE / 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      __hip_atomic_store(exits, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-#endif  // TM_DIAG
-
 // ---------------------------------------------------------------------------
 // host side
 struct Launcher {
@@ -918,7 +776,6 @@ struct Launcher {
   explicit Launcher(int nbh, long long plane, const float* maxima) {
     L.nbh = nbh; L.plane = plane; L.maxima = maxima;
 #ifdef TM_DIAG
-    L.dbg = g_split_dbg;
     L.stamps = g_split_stamps;
 #endif
   }
@@ -945,22 +802,9 @@ struct Launcher {
   }
 };
 
-// the levels [0, nlev) of one direction: one launch per level (or, diagnostic build variant 8,
-// the persistent kernel)
-int run_levels(const ChainArgs& c, int dir, long long plane, const float* maxima, unsigned* ctr, hipStream_t st,
+// the levels [0, nlev) of one direction: one launch per level
+int run_levels(const ChainArgs& c, int dir, long long plane, const float* maxima, hipStream_t st,
                const A3Combine* a3 = nullptr) {
-#ifdef TM_DIAG
-  if (g_split_dbg == 8 || g_split_dbg == 9) {   // 9: plain-policy DMA (timing probe only: L1 may be stale)
-    TeamArgs T{c, dir, plane, maxima, ctr, g_split_stamps};
-    auto kern = g_split_dbg == 8 ? pinv_team_kernel<16> : pinv_team_kernel<0>;
-    tm_allow_smem(kern, STAGE_LDS + EPI_LDS + 64);
-    kern<<<TEAM_GRID, NTHREADS, STAGE_LDS + EPI_LDS + 64, st>>>(T);
-    TM_CHECK_LAUNCH();
-    return 0;
-  }
-#else
-  (void)ctr;
-#endif
   const int nlev = dir == 0 ? fwd_levels(c.iters) : bwd_levels(c.iters);
   for (int lvl = 0; lvl < nlev; ++lvl) {
     Launcher l(c.nbh, plane, maxima);
@@ -976,14 +820,13 @@ int run_levels(const ChainArgs& c, int dir, long long plane, const float* maxima
 }  // namespace
 
 extern "C" long long tm_pinv_split_saved_floats(int nbh, int iters) {
-  // ... + the maxima, then the persistent kernel's two counter sets on 64-B lines
-  return (4LL * iters + 3) * nbh * MAT + 2LL * nbh * NL + 2LL * nbh + 16 + TEAM_CTR_WORDS + 64;
+  // FwdLayout: 4 iters + 3 matrix slots per head, the |X| row / column sums, their per-head maxima
+  return (4LL * iters + 3) * nbh * MAT + 2LL * nbh * NL + 2LL * nbh;
 }
 
 // X: fp32 [nbh][256][256]; Xs: its split planes (tm_nys_sim2_softmax_split).  saved: see FwdLayout;
-// Z_iters (fp32) sits at the start of `saved`.  Two launches: L1 (S = X X^T and the |X| sums /
-// maxima, which couple all heads through c, and the zeroed team counters), then every other
-// level in the persistent kernel.
+// Z_iters (fp32) sits at the start of `saved`.  L1 (S = X X^T and the |X| sums / maxima, which
+// couple all heads through c), then one launch per level.
 int pinv_fwd_split(const float* X, const void* Xs, int nbh, int iters, float* saved, const A3Combine* a3,
                    void* stream);
 
@@ -1020,11 +863,10 @@ int pinv_fwd_split(const float* X, const void* Xs, int nbh, int iters, float* sa
     s.kind = KIND_ABSSUMS;
     l.add(s);
     l.L.X = X; l.L.sums = F.sums(); l.L.maxima_out = maxima;
-    l.L.zero_ctr = F.team_ctr(nbh, 0);   // both counter sets (forward, then backward)
     if (int rc = l.go(st)) return rc;
   }
   const ChainArgs c{(const bf16*)Xs, saved, nullptr, nbh, iters};
-  return run_levels(c, 0, plane, maxima, F.team_ctr(nbh, 0), st, a3);
+  return run_levels(c, 0, plane, maxima, st, a3);
 }
 
 // workspace: G, dT5, dZa, dP, dT3 (split) + dX (fp32) + partial dots
@@ -1034,8 +876,7 @@ extern "C" long long tm_pinv_bwd_split_workspace_floats(int nbh) {
 
 // dZ: the gradient w.r.t. Z_iters as split planes, placed by the caller at the start of `work`
 // (tm_bmm with c_split).  out: dL/dX (softmax == 0) or dL/d(sim2 logits) = softmax backward of
-// A2 = X (softmax != 0), fp32.  `saved` is the forward's; its backward counter set is used (and
-// left zeroed) by the persistent kernel.
+// A2 = X (softmax != 0), fp32.  `saved` is the forward's.
 extern "C" int tm_pinv_bwd_split(const float* X, const void* Xs, int nbh, int iters, const float* saved, float* work,
                                  int softmax, float* out, void* stream) {
   TM_REQUIRE(X && Xs && saved && work && out && nbh > 0 && iters >= 1, "pinv_bwd_split: bad args");
@@ -1049,7 +890,7 @@ extern "C" int tm_pinv_bwd_split(const float* X, const void* Xs, int nbh, int it
   ChainArgs c{(const bf16*)Xs, (float*)saved, work, nbh, iters};
   c.X = X;      // the last level writes G0 and the c gradient's per-wave dots sum G0 o X^T
   c.part = part;
-  if (int rc = run_levels(c, 1, plane, maxima, F.team_ctr(nbh, 1), st)) return rc;
+  if (int rc = run_levels(c, 1, plane, maxima, st)) return rc;
   // Z_0 = X^T / c: the transpose term, the max-tie terms and the softmax
   pinv_apply_bwd_kernel<<<dim3(nbh, NL / APPLY_ROWS), 256, 0, st>>>(X, F.sums(), maxima, G, plane, part, nbh * 16, nbh, dXc,
                                                         softmax, out);
@@ -1058,7 +899,6 @@ extern "C" int tm_pinv_bwd_split(const float* X, const void* Xs, int nbh, int it
 }
 
 #ifdef TM_DIAG
-extern "C" void tm_debug_set_split_variant(int v) { g_split_dbg = v; }
 // diagnostic: per-wave stamps (8 x u64 per wave, 8 waves per workgroup) of every later stage launch; null: off
 extern "C" void tm_debug_set_split_stamps(unsigned long long* buf) { g_split_stamps = buf; }
 #endif

@@ -59,7 +59,7 @@ static_assert(SMT == 8, "two pixel tiles per wave");
 // start, first region staged, its k loop done, its conv tile stored, its pool stores issued,
 // realtime end of the workgroup)
 __device__ unsigned long long g_stem_stamps[4096 * 8];
-int g_stem_variant = 0;
+int g_stem_stamps_on = 0;   // tm_debug_set_stem_stamps: launch the stamped instantiation
 #endif
 template <bool ON>
 TM_DEV void stem_stamp(unsigned long long (&ts)[8], int slot, bool real = false) {
@@ -362,7 +362,7 @@ int stem_setup(StemArgs& a, const void* x, const void* wp, int N, int H, int W, 
 
 template <int MODE>
 int stem_launch(const StemArgs& a, int grid, void* stream) {
-  if (TM_DIAG_VAR(g_stem_variant) == 1) {
+  if (TM_DIAG_VAR(g_stem_stamps_on)) {
     tm_allow_smem(stem_conv_pool_kernel<MODE, true>, SLDS + SRED_BYTES);
     stem_conv_pool_kernel<MODE, true><<<(unsigned)grid, STHREADS, SLDS + SRED_BYTES, (hipStream_t)stream>>>(a);
   } else {
@@ -416,7 +416,7 @@ extern "C" int tm_stem_conv_pool_bn(const void* x, const void* wp, const float* 
 }
 
 #ifdef TM_DIAG
-extern "C" void tm_debug_set_stem_variant(int v) { g_stem_variant = v; }
+extern "C" void tm_debug_set_stem_stamps(int on) { g_stem_stamps_on = on; }
 extern "C" int tm_debug_stem_stamps(unsigned long long* host, int count) {
   TM_REQUIRE(count > 0 && count <= 4096 * 8, "stem_stamps: bad count");
   if (hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stem_stamps), count * sizeof(unsigned long long)) != hipSuccess) {

@@ -18,7 +18,6 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
 from dataclasses import dataclass
 
 import torch
@@ -32,9 +31,9 @@ TAPS = 33       # residual conv
 PINV_ITERS = 6
 LN_EPS = 1e-5
 QROWS = NL + 32  # rows per bag of tm_cls_q_rows' operands (landmarks, class row, zero rows to 32 | rows)
-# bf16 class-row layer: the q part of to_qkv's backward as two small products (TM_CLS_Q_ROWS=0: the
-# dense q block of dqkv, for A/B runs and the equivalence test)
-CLS_Q_ROWS = os.environ.get("TM_CLS_Q_ROWS", "1") != "0"
+# bf16 class-row layer: the q part of to_qkv's backward as two small products (False: the dense q
+# block of dqkv; the equivalence test sets it)
+CLS_Q_ROWS = True
 
 
 class _Probe:
@@ -176,11 +175,9 @@ def cu_count():
     return _CU[dev]
 
 
-# A/B knobs (scripts/dev/ab_env.sh only; defaults are the measured choices): workgroup slots the
-# split-K weight gradients size their splits for (0: one per CU), and the LayerNorm backward's rows
-# per block
-_WGRAD_SLOTS = int(os.environ.get("TM_WGRAD_SLOTS", "0"))
-_LN_BWD_RPB = int(os.environ.get("TM_LN_BWD_RPB", "16"))
+# LayerNorm backward rows per block: 16 = 4 rows per wave, one ahead in flight (partials via the
+# deferred reduce; 4 / 8 / 32 measured slower or level, profiles/r06w_*, r06x_*)
+_LN_BWD_RPB = 16
 
 
 def weight_grad(dY, X, out, M, N, K, *, ldy, ldx, dtype, work_pool, bias_out=None, slab_bf16=None):
@@ -190,7 +187,7 @@ def weight_grad(dY, X, out, M, N, K, *, ldy, ldx, dtype, work_pool, bias_out=Non
     bf16 mode): the split partials are stored bf16 (half the slab bytes written and read back by the
     flush, which sums them in fp32 in split order); False keeps fp32 slabs."""
     tiles = ((M + 127) // 128) * ((N + 127) // 128)
-    slots = _WGRAD_SLOTS or cu_count()
+    slots = cu_count()   # one workgroup slot per CU
     splits = max(1, min(16, slots // max(tiles, 1), (K + 255) // 256))   # <= one workgroup per CU
     if splits == 1:
         gemm(dY, X, out, M, N, K, lda=ldy, ldb=ldx, ldc=N, a_trans=1, b_kn=1, dtype=dtype, c_dtype=F32)
@@ -628,8 +625,7 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
                                         cls_row=pad if saved["cls_only"] else None,
                                         xn=saved["xn"] if qrows_on else None)
     dxn = pool(B * n * D, tdtype).view(B, n, D)
-    rpb = _LN_BWD_RPB   # LN backward rows per block: 16 = 4 rows per wave, one ahead in flight (partials via the
-                        # deferred reduce; 4 / 8 / 32 measured slower or level, profiles/r06w_*, r06x_*)
+    rpb = _LN_BWD_RPB
     if qrows is None:
         # to_qkv: dWqkv = dqkv^T xn ; dxn = dqkv Wqkv
         with defer_reductions(), probe("wgrad_qkv"):
