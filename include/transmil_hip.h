@@ -472,6 +472,39 @@ int tm_step_prepare(int dtype, const tm_cast_table* table, const float* w7, cons
                     float* wfold, float* bfold, long long* counter, long long* seed_out,
                     const float* cls, float* H, int B, int S, void* stream);
 
+/* ---- evaluation record and epoch metrics (evalrec.hip) --------------------
+ * validation_step / test_step and their epoch ends (code/models/model_interface.py:432-607,
+ * 609-860) without a host sync per step.  The epoch record is five caller-owned arrays of
+ * `capacity` rows (logits / prob fp32 [capacity][C], y_hat / label int64, nll fp32) plus a device
+ * int `cursor` (rows appended so far) and class_stats (int32 [C][2] count / correct, as tm_ce_fwd;
+ * may be NULL).
+ * tm_eval_record: one launch per step; for bag b row cursor + b receives the logits, their
+ * max-subtracted fp32 softmax, the first argmax, the label and nll = logsumexp(logits) -
+ * logits[label]; class_stats[label] is bumped and cursor advances by B.  A row >= capacity is not
+ * written (the cursor still counts, so the host sees the overflow at the epoch end); a label
+ * outside [0, C) gives a NaN nll, no stats update and no out-of-bounds read. */
+int tm_eval_record(const float* logits, const long long* label, int B, int C, int capacity, int* cursor,
+                   float* rec_logits, float* rec_prob, long long* rec_yhat, long long* rec_label,
+                   float* rec_nll, int* class_stats, void* stream);
+/* Per patient p in [0, P) over the first M record rows (patient: int32 [M] ids; other ids are
+ * ignored), in record order: target = the label of the first slide, score[C] = the fp32 mean of the
+ * slides' prob (with positive_rule: over the slides with y_hat == 1 only when there is one, :539-544),
+ * pred = score[1] > 0.5 for C == 2, else the first argmax; nslides = the slide count (a patient
+ * without slides: score 0, target -1). */
+int tm_eval_patients(const float* rec_prob, const long long* rec_yhat, const long long* rec_label,
+                     const int* patient, int M, int C, int P, int positive_rule, float* score,
+                     long long* pred, long long* target, int* nslides, void* stream);
+/* cm[target][pred] as int32 [C][C] (= ; out-of-range entries skipped) and, when nll is non-NULL,
+ * nll_sum[0] = the sum of nll[0..M) accumulated in double in a fixed order. */
+int tm_eval_confusion(const long long* pred, const long long* target, int M, int C, int* cm,
+                      const float* nll, double* nll_sum, void* stream);
+/* One-vs-rest Mann-Whitney counts per class c over scores [M][C]: over every (i, j) with
+ * target[i] == c != target[j], wins2[c] = sum 2 [s_i > s_j] + [s_i == s_j], npairs[c] = the pair
+ * count (both uint64 [C], = ).  AUROC_c = wins2 / (2 npairs): the trapezoidal ROC area with ties
+ * counted half.  Integer adds only: exact, independent of order. */
+int tm_eval_auc_pairs(const float* scores, const long long* target, int M, int C,
+                      unsigned long long* wins2, unsigned long long* npairs, void* stream);
+
 /* ---- optimizer step (optim.hip) ----------------------------------------
  * torch.optim.RAdam (L2 decay, code/MyOptimizer/optim_factory.py:77-79) + the
  * Lookahead sync (code/MyOptimizer/lookahead.py, wrapped at optim_factory.py:118-121)

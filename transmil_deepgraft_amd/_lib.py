@@ -156,6 +156,10 @@ _SIGS = {
     "tm_fc1_gelu_bwd": (I, [I, P, P, I, I, I, I, I, P, P, P]),
     "tm_gelu_bwd": (I, [I, P, P, L, P, P]),
     "tm_cast_f32_many": (I, [I, C.POINTER(CastTable), P]),
+    "tm_eval_record": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P]),
+    "tm_eval_patients": (I, [P, P, P, P, I, I, I, I, P, P, P, P, P]),
+    "tm_eval_confusion": (I, [P, P, I, I, P, P, P, P]),
+    "tm_eval_auc_pairs": (I, [P, P, I, I, P, P, P]),
     "tm_radam_counters_len": (L, [L]),
     "tm_radam_lookahead_step": (I, [C.POINTER(OptimTable), P, P, P, P, Fl, Fl, Fl, I, Fl, P]),
 }

@@ -16,7 +16,11 @@ it on MI355X:
                            bucket in two parts, each averaged with one RCCL all_reduce over
                            xGMI, part 0 overlapping layer1's backward (9.64 MB of fp32 grads)
 * ``TransMILTask``      -- ``training_step`` / ``configure_optimizers`` with the reference's
-                           batch format ``(bags[B,n,F], labels[B], (names, patients))``
+                           batch format ``(bags[B,n,F], labels[B], (names, patients))``, and
+                           ``validation_step`` / ``test_step`` with their epoch hooks
+* ``EvalRecord``        -- the evaluation epoch's per-slide record on the device (one HIP launch
+                           per step, no host sync) and the epoch-end metric reductions
+* ``GraphedEvaluation`` -- the evaluation step replayed as one captured hipGraph per bag shape
 """
 from __future__ import annotations
 
@@ -553,8 +557,287 @@ class _CrossEntropyOneHot(torch.autograd.Function):
         return dl, None, None
 
 
+class EvalRecord:
+    """The per-slide record of one evaluation epoch and the epoch-end reductions over it.
+
+    ``validation_step`` / ``test_step`` of the reference end in ``loss.item()``, a Python loop over
+    ``self.data`` and a list of per-slide tensors (code/models/model_interface.py:459-469).  Here
+    a step is one ``tm_eval_record`` launch that writes row ``cursor + b`` of five device arrays
+    (``logits`` / ``prob`` fp32 [capacity, C], ``y_hat`` / ``label`` int64, ``nll`` fp32), bumps
+    ``class_stats`` (int32 [C, 2] count / correct) and advances the device ``cursor``: no host sync,
+    nothing in the launch arguments that changes from step to step, so the step can be captured
+    into a hipGraph.  The host only counts rows (``n``).
+
+    ``append`` grows the storage by doubling before a call that would overflow -- unless a
+    ``GraphedEvaluation`` holds graphs over it (``pin()``): captured launches carry the arrays'
+    addresses, so storage must not move, the kernel drops rows past ``capacity`` while the cursor
+    keeps counting, and ``summary()`` raises.  On CPU tensors the same methods run on torch ops
+    (no HIP), so the task logic is testable without a GPU."""
+
+    _FIELDS = ("logits", "prob", "y_hat", "label", "nll")
+
+    def __init__(self, n_classes: int, capacity: int = 256, device="cpu"):
+        if n_classes < 1 or capacity < 1:
+            raise ValueError("EvalRecord: n_classes >= 1 and capacity >= 1")
+        self.n_classes, self.device = int(n_classes), torch.device(device)
+        self.cursor = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.class_stats = torch.zeros(self.n_classes, 2, dtype=torch.int32, device=self.device)
+        self.n = 0              # rows appended, counted on the host
+        self._pins = 0
+        self._alloc(int(capacity))
+
+    def _alloc(self, capacity):
+        C_, dev = self.n_classes, self.device
+        self.capacity = capacity
+        self.logits = torch.zeros(capacity, C_, dtype=torch.float32, device=dev)
+        self.prob = torch.zeros(capacity, C_, dtype=torch.float32, device=dev)
+        self.y_hat = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        self.label = torch.zeros(capacity, dtype=torch.int64, device=dev)
+        self.nll = torch.zeros(capacity, dtype=torch.float32, device=dev)
+
+    def pin(self):
+        """Storage must not move from now on (a captured graph holds its addresses)."""
+        self._pins += 1
+
+    def unpin(self):
+        self._pins = max(0, self._pins - 1)
+
+    def reset(self):
+        """Clear the record (in place: the arrays, the cursor and the stats keep their addresses)."""
+        self.cursor.zero_()
+        self.class_stats.zero_()
+        self.n = 0
+
+    def _grow(self, need):
+        cap = self.capacity
+        while cap < need:
+            cap *= 2
+        old = [getattr(self, f) for f in self._FIELDS]
+        self._alloc(cap)
+        for f, o in zip(self._FIELDS, old):
+            getattr(self, f)[:self.n].copy_(o[:self.n])
+
+    def write(self, logits, label):
+        """The device side of ``append`` alone (what a captured graph replays): ``logits`` [B, C]
+        fp32 and ``label`` [B] int64, contiguous, on the record's device."""
+        B, C_ = logits.shape
+        if C_ != self.n_classes or label.numel() != B:
+            raise ValueError(f"EvalRecord: logits {tuple(logits.shape)} / {label.numel()} labels for "
+                             f"{self.n_classes} classes")
+        if logits.is_cuda:
+            from . import _lib
+            from .engine import _p, _stream
+            _lib.call("tm_eval_record", _p(logits), _p(label), B, C_, self.capacity, _p(self.cursor),
+                      _p(self.logits), _p(self.prob), _p(self.y_hat), _p(self.label), _p(self.nll),
+                      _p(self.class_stats), _stream())
+            return
+        base = int(self.cursor)
+        lse = torch.logsumexp(logits, dim=1)
+        y_hat = torch.argmax(logits, dim=1)
+        ok = (label >= 0) & (label < C_)
+        picked = logits.gather(1, label.clamp(0, C_ - 1).unsqueeze(1)).squeeze(1)
+        nll = torch.where(ok, lse - picked, torch.full_like(lse, float("nan")))
+        k = max(0, min(B, self.capacity - base))
+        for dst, src in zip((self.logits, self.prob, self.y_hat, self.label, self.nll),
+                            (logits, torch.softmax(logits, dim=1), y_hat, label, nll)):
+            dst[base:base + k] = src[:k]
+        for y, h in zip(label[ok].tolist(), y_hat[ok].tolist()):
+            self.class_stats[y, 0] += 1
+            self.class_stats[y, 1] += int(h == y)
+        self.cursor += B
+
+    def append(self, logits, label):
+        """One step: ``logits`` [B, C] and ``label`` [B] (any float / int dtype) on the record's
+        device.  One launch, no sync."""
+        B = logits.shape[0]
+        if self.n + B > self.capacity and not self._pins:
+            if logits.is_cuda and torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("EvalRecord: the record is full and cannot grow during stream capture "
+                                   "(give it the epoch's capacity up front)")
+            self._grow(self.n + B)
+        self.write(logits.detach().float().contiguous(), label.reshape(-1).to(torch.int64).contiguous())
+        self.n += B
+
+    # ------------------------------------------------------------------ epoch end
+    def summary(self, patients, positive_rule: bool = False):
+        """The epoch-end reductions: ``patients`` is the host list of the ``n`` slides' patient
+        names in append order.  Returns a dict of host values -- ``n``, ``nll_sum``, ``slide_cm`` /
+        ``patient_cm`` ([C][C] target x prediction), ``slide_wins2`` / ``slide_npairs`` /
+        ``patient_wins2`` / ``patient_npairs`` (per class, one-vs-rest), ``patient_score`` [P, C],
+        ``patient_target`` / ``patient_pred`` / ``nslides`` [P], ``patients`` (names in
+        first-appearance order) and ``class_stats``.  On the GPU: one upload of the patient ids, six
+        launches, one device-to-host copy."""
+        M, C_ = self.n, self.n_classes
+        if M < 1:
+            raise ValueError("EvalRecord.summary: no slide recorded")
+        if M > self.capacity:
+            raise RuntimeError(f"EvalRecord: {M} slides appended to a record of capacity {self.capacity} whose "
+                               "storage a captured graph pins; the rows past it were dropped")
+        if len(patients) != M:
+            raise ValueError(f"EvalRecord.summary: {len(patients)} patient names for {M} slides")
+        index, ids = {}, []
+        for p in patients:
+            ids.append(index.setdefault(p, len(index)))
+        names = list(index)
+        P_ = len(names)
+        run = self._summary_hip if self.device.type == "cuda" else self._summary_cpu
+        out = run(ids, M, C_, P_, bool(positive_rule))
+        if out.pop("cursor") != M:
+            raise RuntimeError(f"EvalRecord: the device cursor does not match the {M} slides the host counted")
+        out.update(n=M, patients=names)
+        return out
+
+    def _summary_hip(self, ids, M, C_, P_, positive_rule):
+        from . import _lib
+        from .engine import _p, _stream
+        dev = self.device
+        with torch.cuda.device(dev):
+            pid = torch.tensor(ids, dtype=torch.int32).to(dev)
+            # every result in one buffer of 8-byte words, so one copy brings them all to the host
+            w64 = {"nll_sum": 1, "s_w": C_, "s_n": C_, "p_w": C_, "p_n": C_, "ptarget": P_, "ppred": P_}
+            w32 = {"s_cm": C_ * C_, "p_cm": C_ * C_, "nslides": P_, "stats": 2 * C_, "cursor": 1, "pscore": P_ * C_}
+            off, total = {}, 0
+            for k, v in w64.items():
+                off[k] = (total, total + v)
+                total += v
+            for k, v in w32.items():
+                off[k] = (total, total + (v + 1) // 2)
+                total += (v + 1) // 2
+            buf = torch.zeros(total, dtype=torch.int64, device=dev)
+
+            def seg(t, k, dtype=None):
+                a, b = off[k]
+                s = t[a:b]
+                return s if dtype is None else s.view(dtype)[:w32[k]]
+
+            pscore = seg(buf, "pscore", torch.float32)
+            st = _stream()
+            _lib.call("tm_eval_patients", _p(self.prob), _p(self.y_hat), _p(self.label), _p(pid), M, C_, P_,
+                      int(positive_rule), _p(pscore), _p(seg(buf, "ppred")), _p(seg(buf, "ptarget")),
+                      _p(seg(buf, "nslides", torch.int32)), st)
+            _lib.call("tm_eval_confusion", _p(self.y_hat), _p(self.label), M, C_, _p(seg(buf, "s_cm", torch.int32)),
+                      _p(self.nll), _p(seg(buf, "nll_sum")), st)
+            _lib.call("tm_eval_confusion", _p(seg(buf, "ppred")), _p(seg(buf, "ptarget")), P_, C_,
+                      _p(seg(buf, "p_cm", torch.int32)), None, None, st)
+            _lib.call("tm_eval_auc_pairs", _p(self.prob), _p(self.label), M, C_, _p(seg(buf, "s_w")),
+                      _p(seg(buf, "s_n")), st)
+            _lib.call("tm_eval_auc_pairs", _p(pscore), _p(seg(buf, "ptarget")), P_, C_, _p(seg(buf, "p_w")),
+                      _p(seg(buf, "p_n")), st)
+            seg(buf, "stats", torch.int32).copy_(self.class_stats.reshape(-1))
+            seg(buf, "cursor", torch.int32).copy_(self.cursor)
+            host = buf.cpu()        # the epoch's one device-to-host copy (and its one sync)
+        return {"nll_sum": float(seg(host, "nll_sum").view(torch.float64)[0]),
+                "slide_cm": seg(host, "s_cm", torch.int32).view(C_, C_).tolist(),
+                "patient_cm": seg(host, "p_cm", torch.int32).view(C_, C_).tolist(),
+                "slide_wins2": seg(host, "s_w").tolist(), "slide_npairs": seg(host, "s_n").tolist(),
+                "patient_wins2": seg(host, "p_w").tolist(), "patient_npairs": seg(host, "p_n").tolist(),
+                "patient_score": seg(host, "pscore", torch.float32).view(P_, C_).clone(),
+                "patient_target": seg(host, "ptarget").clone(), "patient_pred": seg(host, "ppred").clone(),
+                "nslides": seg(host, "nslides", torch.int32).tolist(),
+                "class_stats": seg(host, "stats", torch.int32).view(C_, 2).tolist(),
+                "cursor": int(seg(host, "cursor", torch.int32)[0])}
+
+    def _summary_cpu(self, ids, M, C_, P_, positive_rule):
+        prob, y_hat, label = self.prob[:M], self.y_hat[:M], self.label[:M]
+        score = torch.zeros(P_, C_, dtype=torch.float32)
+        target = torch.full((P_,), -1, dtype=torch.int64)
+        nslides = [0] * P_
+        rows = [[] for _ in range(P_)]
+        for i, p in enumerate(ids):
+            rows[p].append(i)
+        for p, r in enumerate(rows):
+            target[p], nslides[p] = label[r[0]], len(r)
+            pos = [i for i in r if int(y_hat[i]) == 1]
+            use = pos if positive_rule and pos else r
+            acc = torch.zeros(C_, dtype=torch.float32)
+            for i in use:               # record order, fp32
+                acc = acc + prob[i]
+            score[p] = acc / float(len(use))
+        pred = (score[:, 1] > 0.5).long() if C_ == 2 else torch.argmax(score, dim=1)
+
+        def confusion(pr, tg):
+            cm = [[0] * C_ for _ in range(C_)]
+            for a, b in zip(tg.tolist(), pr.tolist()):
+                if 0 <= a < C_ and 0 <= b < C_:
+                    cm[a][b] += 1
+            return cm
+
+        def pairs(s, tg):
+            wins2, npairs = [], []
+            for c in range(C_):
+                sp, sn = s[tg == c, c], s[tg != c, c]
+                gt = int((sp[:, None] > sn[None, :]).sum())
+                eq = int((sp[:, None] == sn[None, :]).sum())
+                wins2.append(2 * gt + eq)
+                npairs.append(sp.numel() * sn.numel())
+            return wins2, npairs
+
+        s_w, s_n = pairs(prob, label)
+        p_w, p_n = pairs(score, target)
+        return {"nll_sum": float(self.nll[:M].double().sum()), "slide_cm": confusion(y_hat, label),
+                "patient_cm": confusion(pred, target), "slide_wins2": s_w, "slide_npairs": s_n,
+                "patient_wins2": p_w, "patient_npairs": p_n, "patient_score": score, "patient_target": target,
+                "patient_pred": pred, "nslides": nslides, "class_stats": self.class_stats.tolist(),
+                "cursor": int(self.cursor)}
+
+
+def auroc_from_pairs(wins2, npairs):
+    """AUROC from the one-vs-rest Mann-Whitney counts (the trapezoidal ROC area, ties counted half),
+    in fp64: column 1 for two classes, else the mean over classes with a class that has no positive
+    or no negative counting 0; 0.0 when the targets hold a single class (no pair at all;
+    model_interface.py:500-503, 582-585)."""
+    if len(wins2) < 2 or not any(npairs):
+        return 0.0
+    per = [w / (2.0 * n) if n else 0.0 for w, n in zip(wins2, npairs)]
+    return per[1] if len(per) == 2 else sum(per) / len(per)
+
+
+def metrics_from_confusion(cm, prefix=""):
+    """The reference's metric collection (model_interface.py:186-209) from a confusion matrix
+    ``cm[target][pred]``, in fp64 on the host: Accuracy, CohenKappa, F1Score, Recall, Precision and
+    for more than two classes Specificity.  Two classes: class 1 is the positive one; more: macro
+    averages over all C classes.  An empty denominator gives 0.  Keys are ``prefix`` + the
+    torchmetrics class name (``BinaryF1Score`` / ``MulticlassF1Score`` ...).  torchmetrics itself is
+    not available where this project runs, so parity with it is not pinned; the definitions are
+    (tests/test_eval.py, against NumPy and scikit-learn)."""
+    C_ = len(cm)
+    n = float(sum(sum(r) for r in cm))
+    rows = [float(sum(cm[c])) for c in range(C_)]                       # targets per class
+    cols = [float(sum(cm[t][c] for t in range(C_))) for c in range(C_)]  # predictions per class
+    diag = [float(cm[c][c]) for c in range(C_)]
+
+    def div(a, b):
+        return a / b if b else 0.0
+
+    po = div(sum(diag), n)
+    pe = div(sum(r * c for r, c in zip(rows, cols)), n * n)
+    kappa = div(po - pe, 1.0 - pe)
+    recall = [div(diag[c], rows[c]) for c in range(C_)]
+    precision = [div(diag[c], cols[c]) for c in range(C_)]
+    f1 = [div(2.0 * diag[c], rows[c] + cols[c]) for c in range(C_)]
+    spec = [div(n - rows[c] - cols[c] + diag[c], n - rows[c]) for c in range(C_)]
+    if C_ == 2:
+        return {prefix + "BinaryAccuracy": po, prefix + "BinaryCohenKappa": kappa, prefix + "BinaryF1Score": f1[1],
+                prefix + "BinaryRecall": recall[1], prefix + "BinaryPrecision": precision[1]}
+    mean = lambda v: sum(v) / C_        # noqa: E731
+    return {prefix + "MulticlassAccuracy": mean(recall), prefix + "MulticlassCohenKappa": kappa,
+            prefix + "MulticlassF1Score": mean(f1), prefix + "MulticlassRecall": mean(recall),
+            prefix + "MulticlassPrecision": mean(precision), prefix + "MulticlassSpecificity": mean(spec)}
+
+
+class _EvalState:
+    """One stage's record with the slide / patient names of its rows (host lists, append order)."""
+
+    def __init__(self, record):
+        self.record, self.names, self.patients = record, [], []
+
+    def reset(self):
+        self.record.reset()
+        self.names, self.patients = [], []
+
+
 class TransMILTask(nn.Module):
-    """``ModelInterface`` training-step subset for the feature-bag path."""
+    """``ModelInterface`` training / validation / test step subset for the feature-bag path."""
 
     def __init__(self, model: nn.Module, lr: float = 2e-4, opt: str = "lookahead_radam",
                  weight_decay: float = 0.01, loss: str = "CrossEntropyLoss", accumulate_grad_batches: int = 1):
@@ -642,6 +925,158 @@ class TransMILTask(nn.Module):
             opt.base_optimizer if isinstance(opt, Lookahead) else opt, mode="min", factor=0.5),
             "monitor": "val_loss", "frequency": 10}
         return [opt], [sched]
+
+    # ------------------------------------------------------------------ validation / test
+    # validation_step / on_validation_epoch_end and test_step / on_test_epoch_end of the reference
+    # (model_interface.py:432-607, 609-860) without CSV export, plots and loggers: the step appends
+    # to a device-side EvalRecord (no host sync, capturable), the epoch end reduces it on the device
+    # and derives every metric on the host from one small copy.
+
+    def eval_state(self, stage: str, device=None, capacity: int = 256) -> "_EvalState":
+        """The stage's ("val" / "test") record and name lists, created on first use."""
+        if stage not in ("val", "test"):
+            raise ValueError("stage must be 'val' or 'test'")
+        states = self.__dict__.setdefault("_eval_states", {})    # created by the first evaluation call
+        st = states.get(stage)
+        if st is None or (device is not None and st.record.device != torch.device(device)):
+            if device is None:
+                device = next(self.model.parameters()).device
+            st = states[stage] = _EvalState(EvalRecord(self.n_classes, capacity, device))
+        return st
+
+    def _parse_eval_batch(self, batch):
+        """``(bags, label, (wsi_name, coords_or_names, patient))`` -> bags [B, N, F], the label as a
+        [B] tensor (an int, a CPU or a device tensor; a CPU label outside [0, C) raises IndexError as
+        ``forward_ce`` does) and the B slide / patient names as lists."""
+        bags, label, meta = batch
+        names, patients = meta[0], meta[-1]
+        if bags.dim() == 2:
+            bags = bags.unsqueeze(0)
+        elif bags.dim() > 3:
+            bags = bags.squeeze(0)
+        B = bags.shape[0]
+        if not torch.is_tensor(label):
+            label = torch.as_tensor(label, dtype=torch.int64)
+        label = label.reshape(-1)
+        if label.numel() != B:
+            raise ValueError(f"evaluation step: {label.numel()} labels for {B} bags")
+        if not label.is_cuda and not (0 <= int(label.min()) and int(label.max()) < self.n_classes):
+            raise IndexError(f"evaluation step: labels must lie in [0, {self.n_classes})")
+        names = [names] if isinstance(names, str) else list(names)
+        patients = [patients] if isinstance(patients, str) else list(patients)
+        if len(names) != B or len(patients) != B:
+            raise ValueError(f"evaluation step: {len(names)} slide names / {len(patients)} patients for {B} bags")
+        return bags, label, names, patients
+
+    def _eval_forward_record(self, record, bags, label):
+        """The device side of an evaluation step: the forward (the model in whatever mode it is in,
+        under no_grad) and the record launch.  This is what ``GraphedEvaluation`` captures."""
+        with torch.no_grad():
+            logits = self(bags.float().contiguous())
+            record.write(logits.float().contiguous(), label)
+        return logits
+
+    def _eval_step(self, stage, batch):
+        bags, label, names, patients = self._parse_eval_batch(batch)
+        st = self.eval_state(stage, bags.device)
+        with torch.no_grad():
+            logits = self(bags.float().contiguous())
+            st.record.append(logits, label.to(device=logits.device, dtype=torch.int64))
+        st.names += names            # names stay on the host, in append order
+        st.patients += patients
+        return logits
+
+    def validation_step(self, batch, batch_idx=None):
+        """model_interface.py:432-469: forward, cross entropy, Y_prob, Y_hat and the per-class
+        count / correct of one batch, appended to the validation record in one launch.  No host
+        sync (with a device label): the call can be captured into a hipGraph.  Returns the logits."""
+        return self._eval_step("val", batch)
+
+    def test_step(self, batch, batch_idx=None):
+        """model_interface.py:609-660 without the top-k tile bookkeeping; as ``validation_step``."""
+        return self._eval_step("test", batch)
+
+    def on_validation_epoch_start(self):
+        self.eval_state("val").reset()
+
+    def on_test_epoch_start(self):
+        self.eval_state("test").reset()
+
+    def _gathered(self, st, group):
+        """The ranks' records and name lists as one record in rank order (every rank builds the same
+        one): counts and names first (all_gather_object), then logits and labels padded to the
+        longest rank; the rows are re-derived from the gathered logits by the same launch."""
+        world = dist.get_world_size(group)
+        rec = st.record
+        if rec.n > rec.capacity:
+            raise RuntimeError(f"EvalRecord: {rec.n} slides appended to a pinned record of capacity {rec.capacity}")
+        meta = [None] * world
+        dist.all_gather_object(meta, (rec.n, st.names, st.patients), group=group)
+        counts = [m[0] for m in meta]
+        width = max(max(counts), 1)
+        lg = torch.zeros(width, rec.n_classes, dtype=torch.float32, device=rec.device)
+        lb = torch.zeros(width, dtype=torch.int64, device=rec.device)
+        lg[:rec.n].copy_(rec.logits[:rec.n])
+        lb[:rec.n].copy_(rec.label[:rec.n])
+        lgs = [torch.empty_like(lg) for _ in range(world)]
+        lbs = [torch.empty_like(lb) for _ in range(world)]
+        dist.all_gather(lgs, lg, group=group)
+        dist.all_gather(lbs, lb, group=group)
+        merged = _EvalState(EvalRecord(rec.n_classes, max(sum(counts), 1), rec.device))
+        for r, c in enumerate(counts):
+            if c:
+                merged.record.append(lgs[r][:c], lbs[r][:c])
+                merged.names += list(meta[r][1])
+                merged.patients += list(meta[r][2])
+        return merged
+
+    def _eval_epoch_end(self, stage, group=None):
+        st = self.eval_state(stage)
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            st = self._gathered(st, group)
+        C_ = self.n_classes
+        s = st.record.summary(st.patients, positive_rule=(stage == "val" and C_ == 2))   # :539-544 (val only)
+        out = {f"{stage}_loss": s["nll_sum"] / s["n"],
+               f"{stage}_auc": auroc_from_pairs(s["slide_wins2"], s["slide_npairs"]),
+               f"{stage}_patient_auc": auroc_from_pairs(s["patient_wins2"], s["patient_npairs"])}
+        if stage == "test":
+            out.update(metrics_from_confusion(s["slide_cm"], "test_"))              # :689
+        out.update(metrics_from_confusion(s["patient_cm"], f"{stage}_patient"))     # :587, :841
+        if stage == "val":
+            P_ = len(s["patients"])
+            out["val_accuracy"] = sum(s["patient_cm"][c][c] for c in range(C_)) / float(P_)   # :590
+        out["class_acc"] = [(correct / count if count else None) for count, correct in s["class_stats"]]
+        out["patient_score"] = s["patient_score"]
+        out["patient_target"] = s["patient_target"]
+        out["patients"] = s["patients"]
+        out["slides"] = list(st.names)
+        return out
+
+    def on_validation_epoch_end(self, group=None):
+        """model_interface.py:472-607 as a returned dict instead of ``self.log`` calls: Python floats
+        ``val_loss``, ``val_auc``, ``val_patient_auc``, ``val_accuracy`` (patient level, :590) and the
+        ``val_patient*`` collection, plus ``patient_score`` [P, C], ``patient_target``, ``patients``
+        (names in first-appearance order), ``slides`` and ``class_acc``.
+
+        ``val_loss`` is the mean nll over the recorded slides.  The reference logs a per-step value
+        that Lightning averages with ``batch_size=1``, and its evaluation loaders use batch 1, so the
+        two agree there.  AUROC is the Mann-Whitney pair count with ties counted half; the metric
+        collection comes from the confusion matrices (``metrics_from_confusion``).  Parity with
+        torchmetrics itself is not pinned (the package is absent where this project runs); the
+        definitions are pinned by tests/test_eval.py.
+
+        With a process group of world > 1 every rank all-gathers the ranks' records and names and
+        computes the same global metrics over the union in rank order.  This deviates from the
+        reference, which averages per-rank metrics through ``sync_dist``; it keeps ``val_loss`` --
+        and so the ReduceLROnPlateau scheduler -- identical on all ranks."""
+        return self._eval_epoch_end("val", group)
+
+    def on_test_epoch_end(self, group=None):
+        """model_interface.py:662-860 without CSV / plots / top-k: ``test_loss``, ``test_auc``,
+        ``test_patient_auc``, the slide-level ``test_*`` and patient-level ``test_patient*``
+        collections (patient score: the plain mean over the patient's slides), and the same extra
+        entries as ``on_validation_epoch_end`` (see there for the definitions and the DDP rule)."""
+        return self._eval_epoch_end("test", group)
 
 
 class GraphedOptimizationStep:
@@ -768,3 +1203,102 @@ class GraphedOptimizationStep:
         self.y.copy_(label)
         self.graphs[ph].replay()
         return self.loss[ph]
+
+
+class GraphedEvaluation:
+    """``TransMILTask.validation_step`` / ``test_step`` replayed as captured hipGraphs, one per bag
+    shape.  Evaluation bags are small and differ in size per slide (ceil(0.1 n) tiles), so a forward
+    is bound by launch and host time; the same slides return every epoch, so a graph captured for
+    a shape is replayed from then on.  Same call contract as the step.
+
+    The first time a ``(bags.shape, B)`` is seen the step runs eagerly (it also creates whatever the
+    model caches per shape); the second time the forward plus the record launch are captured over
+    static input / label buffers on one stream and replayed; every later call copies the batch in
+    and replays.  The record's device cursor makes the captured step position-independent.  At most
+    ``max_graphs`` graphs are kept (least recently used out first, ``graph.reset()``).  If any
+    parameter's ``data_ptr`` changed since the captures, all graphs are dropped and built again
+    (in-place optimizer updates do not move parameters, so training between epochs keeps them).
+
+    The record gets ``capacity`` rows up front and is pinned: captured launches hold its addresses,
+    so it cannot grow; an epoch longer than ``capacity`` raises at the epoch end.  Returns the
+    step's logits (a replay returns the graph's static output, overwritten by the next replay of
+    the same shape)."""
+
+    def __init__(self, task: "TransMILTask", stage: str = "val", capacity: int = 4096, max_graphs: int = 64):
+        if max_graphs < 1:
+            raise ValueError("GraphedEvaluation: max_graphs >= 1")
+        self.task, self.stage, self.max_graphs = task, stage, max_graphs
+        device = next(task.model.parameters()).device
+        if device.type != "cuda":
+            raise RuntimeError("GraphedEvaluation needs the model on a GPU")
+        old = task.__dict__.get("_eval_states", {}).pop(stage, None)
+        if old is not None and old.record._pins:
+            raise RuntimeError(f"GraphedEvaluation: another instance holds the '{stage}' record")
+        self.state = task.eval_state(stage, device, capacity)
+        self.state.record.pin()
+        self.graphs = {}        # key -> (graph, static bags, static label, logits), in LRU order
+        self.seen = set()
+        self._pool = None
+        self._ptrs = None
+        self._closed = False
+
+    def _param_ptrs(self):
+        return tuple(p.data_ptr() for p in self.task.model.parameters())
+
+    def _drop(self, keys):
+        if not keys:
+            return
+        torch.cuda.synchronize()                # no replay in flight
+        for k in keys:
+            self.graphs.pop(k)[0].reset()
+        torch.cuda.synchronize()
+
+    def close(self):
+        """Release the captured graphs and unpin the record.  Later calls raise."""
+        if self._closed:
+            return
+        self._drop(list(self.graphs))
+        self.state.record.unpin()
+        self._closed = True
+
+    def live_graphs(self):
+        return len(self.graphs)
+
+    def __call__(self, batch, batch_idx=None):
+        if self._closed:
+            raise RuntimeError("GraphedEvaluation: called after close()")
+        task, st = self.task, self.state
+        if task.eval_state(self.stage) is not st:
+            raise RuntimeError("GraphedEvaluation: the task's record was replaced after the captures")
+        bags, label, names, patients = task._parse_eval_batch(batch)
+        rec = st.record
+        ptrs = self._param_ptrs()
+        if ptrs != self._ptrs:                  # parameters moved: every graph reads stale addresses
+            self._drop(list(self.graphs))
+            self.seen.clear()
+            self._ptrs = ptrs
+        key = (tuple(bags.shape), bags.dtype)
+        hit = self.graphs.pop(key, None)
+        if hit is None and key not in self.seen:
+            self.seen.add(key)
+            return task._eval_step(self.stage, (bags, label, (names, None, patients)))
+        if hit is None:
+            x = bags.detach().clone()
+            y = label.to(device=x.device, dtype=torch.int64).clone()
+            if self._pool is None:
+                self._pool = torch.cuda.graph_pool_handle()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=self._pool):
+                logits = task._eval_forward_record(rec, x, y)
+            hit = (g, x, y, logits)
+        else:
+            hit[1].copy_(bags)
+            hit[2].copy_(label)
+        self.graphs[key] = hit                  # most recently used last
+        hit[0].replay()
+        rec.n += bags.shape[0]
+        st.names += names
+        st.patients += patients
+        if len(self.graphs) > self.max_graphs:
+            self._drop(list(self.graphs)[:len(self.graphs) - self.max_graphs])
+        return hit[3]
