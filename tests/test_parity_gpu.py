@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from golden_util import load, bag_input
+from kernel_refs import dropout_keep
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -292,29 +293,6 @@ def test_train_mode_dropout_is_applied_and_reproducible():
         e = ours(x)
     assert torch.equal(a, b)
     assert not torch.equal(a, c) and not torch.equal(a, e)
-
-
-def _mix32(h):
-    h = h.astype(np.uint32)
-    h ^= h >> np.uint32(16)
-    h = (h * np.uint32(0x85EBCA6B)).astype(np.uint32)
-    h ^= h >> np.uint32(13)
-    h = (h * np.uint32(0xC2B2AE35)).astype(np.uint32)
-    h ^= h >> np.uint32(16)
-    return h
-
-
-def dropout_keep(seed_dev_value, layer_seed, rows, cols, p):
-    """Host restatement of common.h dropout_u01 / effective_seed (the kernels' hash)."""
-    seed = (int(seed_dev_value) * 0x9E3779B97F4A7C15 + int(layer_seed)) & (2 ** 64 - 1)
-    lo, hi = np.uint32(seed & 0xFFFFFFFF), np.uint32(seed >> 32)
-    r = np.arange(rows, dtype=np.uint32)[:, None]
-    c = np.arange(cols, dtype=np.uint32)[None, :]
-    with np.errstate(over="ignore"):
-        h = _mix32(lo ^ _mix32((r * np.uint32(0x9E3779B1) + hi).astype(np.uint32)))
-        h = _mix32(h ^ (c * np.uint32(0x7FEB352D)).astype(np.uint32))
-    u = (h >> np.uint32(8)).astype(np.float64) / 16777216.0
-    return u >= p
 
 
 @pytest.mark.parametrize("N,ncls,dtype,ltol,gtol", [

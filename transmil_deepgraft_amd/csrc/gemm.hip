@@ -1551,6 +1551,16 @@ extern "C" int tm_splitk_reduce(const float* slab, float* out, int splits, long 
     push_reduce_entry(q->t, slab, 0, out, splits, count, alpha, accumulate);
     return 0;
   }
+  {
+    // many splits over few outputs: the flush launch gives every output several lanes (par > 1), a
+    // different fixed order from the one-thread loop of splitk_reduce_kernel.  Run that form now too,
+    // so the immediate and the deferred reduce stay bit-identical (the header's promise); up to 24
+    // splits both are the plain index-order sum.
+    tm_reduce_queue local{};
+    local.magic = RQ_MAGIC;
+    push_reduce_entry(local.t, slab, 0, out, splits, count, alpha, accumulate);
+    if (local.t.e[0].par > 1) return tm_reduce_flush(&local, stream);
+  }
   hipStream_t st = (hipStream_t)stream;
   // float4 per thread only when that still gives >= 1024 workgroups' worth of threads
   const bool vec4 = count % 4 == 0 && count / 4 >= 256LL * 1024;
