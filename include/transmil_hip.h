@@ -223,6 +223,29 @@ int tm_nys_assemble_q_slab(int dtype, const float* dq, int dq_row, const float* 
 int tm_nys_assemble_q_slab_inplace(const float* dql, const void* slab, int slabs, int nbags, int nh, int n,
                                    float scale, void* dqkv, void* stream);
 
+/* ---- exact softmax attention (attention.hip) ------------------------------
+ * TransformerMIL's ViT blocks (code/models/_transformer.py:33-43): softmax(q k^T * scale) v, dh = 64,
+ * no mask, not causal, no dropout on the probabilities.  q, k, v, out, dout, dqkv are fp32 in memory.
+ * Element (b, t, h, d) of q / k / v is at base[(b*n + t)*row_stride + h*64 + d], so the packed to_qkv
+ * output [B, n, 3*H*64] is passed as three base pointers with row_stride = 3*H*64.
+ * compute = TM_F32: fp32 MFMA products (exact fmaf chains).  TM_BF16: operands rounded to bf16 while
+ * they are staged, bf16 MFMA, fp32 accumulation; fp32 softmax statistics in both.
+ * out [B, n, H*64] (heads merged, what to_out reads), lse [B*H, n] = log sum_j exp(scale * q.k_j).
+ * Online softmax over 64-key chunks: no n x n matrix is written, any n >= 1.  Arguments are checked
+ * before any device work (n, B, H > 0, B*H <= 65535, row_stride >= H*64 and a multiple of 4, pointers
+ * non-null and 16-byte aligned). */
+int tm_attn_fwd(int compute, const float* q, const float* k, const float* v, int B, int H, int n,
+                long long row_stride, float scale, float* out, float* lse, void* stream);
+/* bytes of tm_attn_bwd's work: D = rowsum(dout o out) as [B*H, n] fp32, linear in B*H*n */
+long long tm_attn_bwd_workspace(int B, int H, int n);
+/* dqkv [B, n, 3*H*64] packed (written, not accumulated): the dY that to_qkv's backward GEMMs read.
+ * P = exp(scale*S - lse) is recomputed; dV = P^T dout and dK = scale * dS^T q come from a pass that owns
+ * its key rows, dQ = scale * dS k from a pass that owns its query rows: no atomics, one writer and one
+ * summation order per element. */
+int tm_attn_bwd(int compute, const float* q, const float* k, const float* v, const float* out,
+                const float* lse, const float* dout, int B, int H, int n, long long row_stride,
+                float scale, void* work, float* dqkv, void* stream);
+
 /* ---- pseudo-inverse + small fp32 batched products (pinv.hip) -------------
  * moore_penrose_iter_pinv of nystrom_attention (App. A eq. 7).
  * C = diag*I + alpha*(op(A) op(B) [+ op(A2) op(B2)]) + e1*E1 + e2*E2, batched;

@@ -101,6 +101,9 @@ _SIGS = {
     "tm_nys_assemble_q_slab": (I, [I, P, I, P, P, I, I, I, I, Fl, P, P]),
     "tm_nys_assemble_q_slab_inplace": (I, [P, P, I, I, I, I, Fl, P, P]),
     "tm_nys_attn_row": (I, [I, P, P, P, P, P, P, I, I, I, P, P]),
+    "tm_attn_fwd": (I, [I, P, P, P, I, I, I, L, Fl, P, P, P]),
+    "tm_attn_bwd_workspace": (L, [I, I, I]),
+    "tm_attn_bwd": (I, [I, P, P, P, P, P, P, I, I, I, L, Fl, P, P, P]),
     "tm_bmm": (I, [C.POINTER(BmmJob), I, I, I, P]),
     "tm_pinv_saved_floats": (L, [I, I]),
     "tm_pinv_fwd": (I, [P, I, I, I, P, P]),

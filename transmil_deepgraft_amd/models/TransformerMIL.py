@@ -4,9 +4,10 @@ code/models/_transformer.py:6-58) on the MI355X kernels.
 Same constructor, parameter names and ``forward(x) -> logits``: ``fc1``, class token,
 Dropout(0.5), two 2-deep pre-norm transformers (full softmax attention, 8 heads x 64, MLP
 512 -> 512), class token -> LayerNorm -> ``_fc2``.  The Linear layers and LayerNorms run on
-the HIP GEMM / LayerNorm kernels; the softmax attention core is
-``torch.nn.functional.scaled_dot_product_attention`` (the ROCm flash path in bf16 mode; this
-sibling head is outside the NystromAttention hot path).  ``pos_layer_0``, ``conv1/2`` and
+the HIP GEMM / LayerNorm kernels; the softmax attention core is ``ops.attention`` (the exact
+online-softmax kernels of ``csrc/attention.hip``, forward and backward, read straight from the
+packed ``to_qkv`` output) in both compute modes: caller-owned buffers, no host sync, no atomics,
+bitwise reproducible, memory linear in the bag size.  ``pos_layer_0``, ``conv1/2`` and
 ``layer1/2`` are constructed for state_dict compatibility and unused, as in the reference.
 """
 from __future__ import annotations
@@ -40,7 +41,7 @@ class Attention(nn.Module):
     def __init__(self, dim=512, heads=8, dim_head=64, dropout=0.1):
         super().__init__()
         inner = dim_head * heads
-        self.heads, self.scale = heads, dim_head ** -0.5
+        self.heads, self.dim_head, self.scale = heads, dim_head, dim_head ** -0.5
         self.to_qkv = nn.Linear(dim, inner * 3, bias=False)
         self.project_out = not (heads == 1 and dim_head == dim)
         self.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout)) if self.project_out else nn.Identity()
@@ -48,10 +49,13 @@ class Attention(nn.Module):
     def forward(self, x):
         b, n, _ = x.shape
         qkv = ops.linear(self.to_qkv, x)
-        q, k, v = (t.reshape(b, n, self.heads, -1).transpose(1, 2) for t in qkv.chunk(3, dim=-1))
         dt = self.compute_dtype
-        o = F.scaled_dot_product_attention(q.to(dt), k.to(dt), v.to(dt), scale=self.scale).float()
-        o = o.transpose(1, 2).reshape(b, n, -1)
+        if self.dim_head == 64:
+            o = ops.attention(qkv, self.heads, self.scale, dt)
+        else:                                                        # a head width TransformerMIL never builds
+            q, k, v = (t.reshape(b, n, self.heads, -1).transpose(1, 2) for t in qkv.chunk(3, dim=-1))
+            o = F.scaled_dot_product_attention(q.to(dt), k.to(dt), v.to(dt), scale=self.scale).float()
+            o = o.transpose(1, 2).reshape(b, n, -1)
         if not self.project_out:
             return o
         return self.to_out[1](ops.linear(self.to_out[0], o))
@@ -114,7 +118,7 @@ class TransformerMIL(nn.Module):
         self.pool = "cls"
 
     def set_compute_dtype(self, dtype):
-        """bf16: the attention core runs in bf16 (flash); fp32 otherwise."""
+        """bf16: the attention core runs on the bf16 MFMA (fp32 statistics); fp32 MFMA otherwise."""
         for m in self.modules():
             if isinstance(m, Attention):
                 m.compute_dtype = dtype

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._lib import F32
+from ._lib import BF16, F32
 from .engine import Geometry, Pool, _p, _stream, LN_EPS, colsum, gemm, weight_grad
 
 
@@ -249,3 +249,49 @@ def linear(module, x):
     if not x.is_cuda:
         raise RuntimeError("HIP Linear needs a GPU tensor")
     return _LinearFn.apply(x.float(), module.weight, module.bias)
+
+
+class _AttentionFn(torch.autograd.Function):
+    """softmax(q k^T scale) v per head over the packed to_qkv output [b, n, 3*heads*64] (fp32),
+    read in place: out [b, n, heads*64]; backward writes the packed dqkv (attention.hip)."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads, scale, compute):
+        b, n, _ = qkv.shape
+        inner = heads * 64
+        qkv = qkv.contiguous()
+        out = torch.empty(b, n, inner, device=qkv.device)
+        lse = torch.empty(b * heads, n, device=qkv.device)
+        q, k, v = (C.c_void_p(qkv.data_ptr() + i * inner * 4) for i in range(3))
+        _lib.call("tm_attn_fwd", compute, q, k, v, b, heads, n, 3 * inner, C.c_float(scale), _p(out), _p(lse),
+                  _stream())
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.args = (heads, scale, compute)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, out, lse = ctx.saved_tensors
+        heads, scale, compute = ctx.args
+        b, n, _ = qkv.shape
+        inner = heads * 64
+        dout = dout.float().contiguous()
+        dqkv = torch.empty_like(qkv)
+        work = torch.empty(_lib.query("tm_attn_bwd_workspace", b, heads, n) // 4, device=qkv.device)
+        q, k, v = (C.c_void_p(qkv.data_ptr() + i * inner * 4) for i in range(3))
+        _lib.call("tm_attn_bwd", compute, q, k, v, _p(out), _p(lse), _p(dout), b, heads, n, 3 * inner,
+                  C.c_float(scale), _p(work), _p(dqkv), _stream())
+        return dqkv, None, None, None
+
+
+def attention(qkv, heads, scale, compute_dtype=torch.float32):
+    """Exact multi-head softmax attention (dim_head 64, no mask) on the HIP kernels: ``qkv`` is the
+    packed ``to_qkv`` output [b, n, 3*heads*64]; returns the merged heads [b, n, heads*64] (fp32).
+    ``compute_dtype``: torch.float32 (fp32 MFMA) or torch.bfloat16 (bf16 MFMA, fp32 statistics)."""
+    if not qkv.is_cuda:
+        raise RuntimeError("HIP attention needs a GPU tensor")
+    if qkv.dim() != 3 or qkv.shape[-1] != 3 * heads * 64:
+        raise ValueError(f"attention expects [b, n, 3*heads*64], got {tuple(qkv.shape)} for heads={heads}")
+    if compute_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attention: compute_dtype must be float32 or bfloat16, got {compute_dtype}")
+    return _AttentionFn.apply(qkv.float(), heads, float(scale), BF16 if compute_dtype == torch.bfloat16 else F32)
