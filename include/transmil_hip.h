@@ -177,6 +177,10 @@ int tm_nys_conv_bwd(int dtype, const void* dmerged, const void* merged, const vo
                     int nbh, int nh, int n, void* dv, float* d1, float* work, float* dwconv,
                     tm_reduce_queue* rq, void* stream);
 long long tm_nys_a1_bwd_workspace(int nbh, int n, int queries_per_wg);
+/* A1 product backward: dq [B*h, n, 64] fp32 written, dkl / dy [B*h, 256, 64] from per-workgroup
+ * partial slabs in work.  queries_per_wg: a multiple of 32 that divides n; the fp32 kernel gives each
+ * workgroup that many query rows, the bf16 kernel splits the rows evenly itself and stages at most
+ * 256 per workgroup, so TM_BF16 with queries_per_wg > 256 is refused (returns 1). */
 int tm_nys_a1_bwd(int dtype, const void* q, const void* dmerged, const void* kl_t, const void* y_t,
                   const float* lse1, const float* d1, int nbh, int nh, int n, int queries_per_wg,
                   float* dq, float* work, float* dkl, float* dy, int accumulate, tm_reduce_queue* rq,

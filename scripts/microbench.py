@@ -24,7 +24,7 @@ from transmil_deepgraft_amd import _lib  # noqa: E402
 from transmil_deepgraft_amd import engine as E  # noqa: E402
 from transmil_deepgraft_amd._lib import BF16, F32  # noqa: E402
 
-# the diagnostic build's selectors: enum GemmSel (csrc/gemm.hip), enum NysSel (csrc/nystrom.hip)
+# the diagnostic build's selectors: enum GemmSel (csrc/gemm.hip), enum NysSel (csrc/nystrom_bf16.h)
 GEMM_SEL = {"auto": 0, "force_reg": 1, "force_ring": 2, "force_ring160": 3, "force_big": 4,
             "stamp_ring": 5, "stamp_big": 6}
 NYS_SEL = {"auto": 0, "stamp_a1_fwd": 1, "stamp_a3_fwd": 2, "stamp_a1_bwd": 3, "stamp_a1_bwd_chunk": 4,

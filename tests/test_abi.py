@@ -74,6 +74,16 @@ def test_error_path_without_gpu():
     assert "multiple of 256" in _lib.last_error()
 
 
+def test_a1_bwd_refuses_bf16_with_more_than_256_queries_per_wg():
+    """tm_nys_a1_bwd(TM_BF16, queries_per_wg > 256) is refused before any launch, naming the limit (the
+    bf16 kernel stages at most 256 query rows per workgroup; no bf16 kernel serves a larger block)."""
+    from transmil_deepgraft_amd import _lib
+    with pytest.raises(RuntimeError, match="queries_per_wg must be <= 256 in bf16 mode"):
+        _lib.call("tm_nys_a1_bwd", _lib.BF16, None, None, None, None, None, None, 8, 8, 1024, 512,
+                  None, None, None, None, 0, None, None)
+    assert "<= 256" in _lib.last_error()
+
+
 def test_build_info():
     from transmil_deepgraft_amd import _lib
     assert b"gfx950" in _lib.lib().tm_build_info()

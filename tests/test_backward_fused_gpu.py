@@ -121,7 +121,7 @@ def test_a3_bwd_fused_key_side_and_slabs(nbh, n, lo, hi):
         want = bf16(unfused dk + p32), p32 = fp32(dk~[t // l] * fp32(1 / l)), all in fp32:
         "within one bf16 ulp" held at l = 1 (0 ulp) and l = 3 (1 ulp) but not at l >= 5 (2 ulps at 8
         heads, 10 at 16 x 8448 measured).  The differing operation: the epilogue's
-        `*sk + ak * il` (nystrom.hip, the fused branch of attn_bwd_bf16_kernel) is compiled with
+        `*sk + ak * il` (nystrom_bf16.h, the fused branch of attn_bwd_bf16_kernel) is compiled with
         fp contraction on, so it is fma(dk~, 1/l, dK): the product is not rounded to fp32 first.
         That moves the fp32 sum by up to half an fp32 ulp OF THE PRODUCT, which is many ulps of the
         sum where dK and dk~ / l cancel.  Derived bound (not a loosening to a looser constant):

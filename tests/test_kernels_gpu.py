@@ -800,6 +800,17 @@ def test_cls_q_rows_against_torch(B, n, nslabs):
     assert (Aq[:, NL + 1:] == 0).all() and (Xs[:, NL + 1:] == 0).all()
 
 
+def _a1_bwd_ref(q, kl, y, dm, lse, d1, nh):
+    """fp64 per head: P = exp(q k~^T - lse), dS = P o (dO Y^T - D); dq = dS k~, dk~ = dS^T q,
+    dY = P^T dO (dm: the merged-layout dO [bags][n][nh * 64])."""
+    nbh, n, _ = q.shape
+    dO = dm.double().view(nbh // nh, n, nh, 64).permute(0, 2, 1, 3).reshape(nbh, n, 64)
+    qf, kf, yf = q.double(), kl.double(), y.double()
+    P = torch.exp(qf @ kf.transpose(1, 2) - lse.double()[..., None])
+    dS = P * (dO @ yf.transpose(1, 2) - d1.double()[..., None])
+    return dS @ kf, dS.transpose(1, 2) @ qf, P.transpose(1, 2) @ dO
+
+
 @pytest.mark.parametrize("deferred", [False, True])
 @pytest.mark.parametrize("nbags,n", [(1, 8448), (2, 1024)])
 def test_a1_bwd_bf16_landmark_and_y_grads_vs_fp64(nbags, n, deferred):
@@ -836,13 +847,7 @@ def test_a1_bwd_bf16_landmark_and_y_grads_vs_fp64(nbags, n, deferred):
     finally:
         if deferred:
             L.lib().tm_reduce_queue_destroy(rq)
-    # fp64 reference per head
-    dO = dm.double().view(nbags, n, nh, 64).permute(0, 2, 1, 3).reshape(nbh, n, 64)
-    qf, kf, yf = q.double(), kl.double(), y.double()
-    P = torch.exp(qf @ kf.transpose(1, 2) - lse.double()[..., None])
-    dS = P * (dO @ yf.transpose(1, 2) - d1.double()[..., None])
-    ek = dS.transpose(1, 2) @ qf
-    ey = P.transpose(1, 2) @ dO
+    _, ek, ey = _a1_bwd_ref(q, kl, y, dm, lse, d1, nh)
     ak, ay = dkl.cpu(), dy.cpu()
     rk, ry = _rel(ak, ek), _rel(ay, ey)
     # bf16 partials (2^-9 each) over fp32 sums of bf16 products: well inside 4e-3 of the max
@@ -912,3 +917,154 @@ def test_a1_bwd_dqkv_bf16_path_equals_the_fp32_dq_path(nbags, n):
     bound = 0.5 * ulp(sdq) + ulp(qb)
     assert ((qa - qb).abs() <= bound * 1.0001 + 1e-30).all(), ((qa - qb).abs() - bound).max()
     assert (a[0][..., nh * 64:] == sentinel).all()
+
+
+# ----------------------------------------------------------------------------- fp32 (parity-mode) Nystrom kernels
+# The fp32 kernels of csrc/nystrom_f32.h through their entry points, on fp32 operands (not rounded
+# to bf16), against the fp64 restatements above; outputs prefilled with NaN.  Each _f32_* helper runs
+# one call and returns {output: (got, fp64 reference, "rel" | "abs")}: "rel" is _rel, "abs" the largest
+# absolute error (the log-sum-exp outputs and D1).  The products are exact in fp32, so the error is
+# the rounding of the fp32 sums alone.  Each bound is 4x the worst figure over the output's cases as
+# measured with the library of the commit before the kernels lost their template parameter (listed
+# beside it), the margin leaving room for a later reorder of a reduction; every bound is far inside
+# the 1e-4 that test_nystrom_attention_fp32_vs_oracle allows the whole module.
+def _f32_setup(seed):
+    from transmil_deepgraft_amd.engine import _p, _stream
+    from transmil_deepgraft_amd._lib import F32
+    return _lib(), F32, _p, _stream, torch.Generator(device="cpu").manual_seed(seed)
+
+
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+def _f32_errors(figs):
+    """{output: error} of a helper's result; every output must be finite (no NaN prefill left)."""
+    errs = {}
+    for name, (got, ref, kind) in figs.items():
+        assert torch.isfinite(got).all(), name
+        errs[name] = _rel(got, ref) if kind == "rel" else (got.double() - ref).abs().max().item()
+    print(" ".join(f"{k}={v:.3e}" for k, v in errs.items()))
+    return errs
+
+
+def _f32_a1_fwd(nbh, n):
+    L, F32, _p, _stream, g = _f32_setup(n + nbh)
+    nh = 8
+    q = torch.randn(nbh, n, 64, generator=g) * 0.3
+    v = torch.randn(nbh, n, 64, generator=g)
+    kl = torch.randn(nbh, 256, 64, generator=g) * 0.3
+    y = torch.randn(nbh, 256, 64, generator=g)
+    wconv = torch.randn(nh, 33, generator=g) * 0.1
+    ref_m, ref_l = _a1_ref(q, v, kl, y, wconv, nh)
+    merged, lse = _nan(nbh // nh, n, nh * 64), _nan(nbh, n)
+    qd, vd, kd, yd, wd = (t.to(DEV).contiguous() for t in (q, v, kl, y, wconv))
+    L.call("tm_nys_a1_fwd", F32, _p(qd), _p(vd), _p(kd), _p(yd), _p(wd), nbh, nh, n, _p(merged), _p(lse), _stream())
+    torch.cuda.synchronize()
+    return {"merged": (merged.cpu(), ref_m, "rel"), "lse1": (lse.cpu(), ref_l, "abs")}
+
+
+def _f32_a3_fwd(nbh, n):
+    L, F32, _p, _stream, g = _f32_setup(n + 7 * nbh)
+    ql = torch.randn(nbh, 256, 64, generator=g) * 0.4
+    k = torch.randn(nbh, n, 64, generator=g) * 0.4
+    v = torch.randn(nbh, n, 64, generator=g)
+    s = ql.double() @ k.double().transpose(1, 2)
+    ref_lse, ref_w = torch.logsumexp(s, -1), torch.softmax(s, -1) @ v.double()
+    w, lse = _nan(nbh, 256, 64), _nan(nbh, 256)
+    work = torch.empty(L.query("tm_nys_a3_workspace", nbh, n) // 4 + 16, device=DEV)
+    qd, kd, vd = (t.to(DEV).contiguous() for t in (ql, k, v))
+    L.call("tm_nys_a3_fwd", F32, _p(qd), _p(kd), _p(vd), nbh, n, _p(work), _p(w), _p(lse), _stream())
+    torch.cuda.synchronize()
+    return {"w": (w.cpu(), ref_w, "rel"), "lse3": (lse.cpu(), ref_lse, "abs")}
+
+
+def _f32_conv_bwd(nbags, n):
+    L, F32, _p, _stream, g = _f32_setup(n * 7 + nbags)
+    nh = 8
+    nbh = nbags * nh
+    dO = torch.randn(nbags, n, nh * 64, generator=g) * 0.5
+    O = torch.randn(nbags, n, nh * 64, generator=g)
+    v = torch.randn(nbh, n, 64, generator=g)
+    wconv = torch.randn(nh, 33, generator=g) * 0.1
+    ref_dv, ref_d1, ref_dw = _conv_bwd_ref(dO, O, v, wconv, nh)
+    dv, d1, dw = _nan(nbh, n, 64), _nan(nbh, n), _nan(nh * 33)
+    work = torch.empty(L.query("tm_nys_conv_bwd_workspace", nbags, nh, n) // 4 + 16, device=DEV)
+    dOd, Od, vd, wd = (t.to(DEV).contiguous() for t in (dO, O, v, wconv))
+    L.call("tm_nys_conv_bwd", F32, _p(dOd), _p(Od), _p(vd), _p(wd), nbh, nh, n, _p(dv), _p(d1), _p(work),
+           _p(dw), None, _stream())
+    torch.cuda.synchronize()
+    return {"dv": (dv.cpu(), ref_dv, "rel"), "d1": (d1.cpu(), ref_d1, "abs"),
+            "dw": (dw.cpu().view(nh, 33), ref_dw, "rel")}
+
+
+def _f32_a3_bwd(nbh, n):
+    L, F32, _p, _stream, g = _f32_setup(n * 3 + nbh)
+    ql = torch.randn(nbh, 256, 64, generator=g) * 0.3
+    dw = torch.randn(nbh, 256, 64, generator=g) * 0.1
+    k = torch.randn(nbh, n, 64, generator=g) * 0.3
+    v = torch.randn(nbh, n, 64, generator=g)
+    lse, d, ref_dk, ref_dv, ref_dql = _a3_bwd_ref(ql, dw, k, v)
+    # D as the [2][nbh][256] partials over the two 32-column halves, as the engine passes it
+    wv = torch.softmax(ql.double() @ k.double().transpose(1, 2), -1) @ v.double()
+    dparts = torch.stack([(dw.double() * wv)[..., :32].sum(-1), (dw.double() * wv)[..., 32:].sum(-1)])
+    dk, dql = _nan(nbh, n, 64), _nan(nbh, 256, 64)
+    dv = torch.zeros(nbh, n, 64, device=DEV)           # accumulated into (+=)
+    work = torch.empty(L.query("tm_nys_a3_bwd_workspace", nbh, n) // 4 + 16, device=DEV)
+    qd, wd, kd, vd, lsed, dd = (t.to(DEV).contiguous() for t in (ql, dw, k, v, lse.float(), dparts.float()))
+    L.call("tm_nys_a3_bwd", F32, _p(qd), _p(wd), _p(kd), _p(vd), _p(lsed), _p(dd), nbh, 8, n,
+           _p(dk), _p(dv), _p(work), _p(dql), 0, None, _stream())
+    torch.cuda.synchronize()
+    return {"dk": (dk.cpu(), ref_dk, "rel"), "dv": (dv.cpu(), ref_dv, "rel"), "dql": (dql.cpu(), ref_dql, "rel")}
+
+
+def _f32_a1_bwd(nbh, n):
+    L, F32, _p, _stream, g = _f32_setup(29 + n + nbh)
+    nh = 8
+    q = torch.randn(nbh, n, 64, generator=g) * 0.3
+    kl = torch.randn(nbh, 256, 64, generator=g) * 0.3
+    y = torch.randn(nbh, 256, 64, generator=g)
+    dm = torch.randn(nbh // nh, n, nh * 64, generator=g) * 0.1
+    lse = torch.logsumexp(q.double() @ kl.double().transpose(1, 2), -1).float()   # a consistent softmax
+    d1 = torch.randn(nbh, n, generator=g) * 0.05
+    ref_dq, ref_dk, ref_dy = _a1_bwd_ref(q, kl, y, dm, lse, d1, nh)
+    dq, dkl, dy = _nan(nbh, n, 64), _nan(nbh, 256, 64), _nan(nbh, 256, 64)
+    work = torch.empty(L.query("tm_nys_a1_bwd_workspace", nbh, n, 256) // 4 + 16, device=DEV)
+    qd, kd, yd, dmd, lsed, d1d = (t.to(DEV).contiguous() for t in (q, kl, y, dm, lse, d1))
+    L.call("tm_nys_a1_bwd", F32, _p(qd), _p(dmd), _p(kd), _p(yd), _p(lsed), _p(d1d), nbh, nh, n, 256,
+           _p(dq), _p(work), _p(dkl), _p(dy), 0, None, _stream())
+    torch.cuda.synchronize()
+    return {"dq": (dq.cpu(), ref_dq, "rel"), "dkl": (dkl.cpu(), ref_dk, "rel"), "dy": (dy.cpu(), ref_dy, "rel")}
+
+
+# (helper, cases, {output: bound}); each bound = 4 x the worst figure over its cases, measured on an
+# MI355X with the parent commit's library (the figures are in the trailing comments; this tree's
+# kernels gave the same bits)
+_F32_CASES = {
+    # two 128-row blocks (the conv halo crosses a block edge), per-head taps; then two bags
+    "a1_fwd": (_f32_a1_fwd, [(8, 256), (16, 512)],
+               {"merged": 1.08e-6, "lse1": 3.61e-6}),                   # 2.70e-7, 9.02e-7
+    # one key block; then an odd number of partials through a3_combine_kernel
+    "a3_fwd": (_f32_a3_fwd, [(8, 256), (8, 768)],
+               {"w": 6.00e-6, "lse3": 3.45e-6}),                        # 1.50e-6, 8.63e-7
+    # (nbags, n): a ragged last block; then the weight gradient summed over bags
+    "conv_bwd": (_f32_conv_bwd, [(1, 100), (4, 300)],
+                 {"dv": 8.81e-7, "d1": 9.79e-6, "dw": 9.98e-7}),        # 2.20e-7, 2.45e-6, 2.49e-7
+    # one key block; then the slab reduce over 3 key blocks, two bags
+    "a3_bwd": (_f32_a3_bwd, [(8, 256), (16, 768)],
+               {"dk": 3.16e-6, "dv": 3.24e-6, "dql": 2.08e-6}),         # 7.91e-7, 8.11e-7, 5.19e-7
+    # queries_per_wg = 256: one workgroup per head; then 3 query blocks (slab reduce), two bags
+    "a1_bwd": (_f32_a1_bwd, [(8, 256), (16, 768)],
+               {"dq": 2.78e-6, "dkl": 3.03e-6, "dy": 3.29e-6}),         # 6.95e-7, 7.56e-7, 8.22e-7
+}
+
+
+@pytest.mark.parametrize("kernel,case", [(k, c) for k, (_, cases, _) in _F32_CASES.items() for c in cases])
+def test_nystrom_f32_kernels_vs_fp64(kernel, case):
+    """The fp32 parity kernels (a1_fwd, a3_fwd + a3_combine, conv_bwd, attn_bwd<A3>, attn_bwd<A1>)
+    on fp32 operands against fp64, at the smallest shapes that exercise each kernel's indexing."""
+    helper, _, bounds = _F32_CASES[kernel]
+    errs = _f32_errors(helper(*case))
+    assert set(errs) == set(bounds)
+    for name, err in errs.items():
+        assert err < bounds[name], (name, err, bounds[name])

@@ -29,7 +29,7 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // Diagnostic selectors exist only in the TM_DIAG build (`make diag` -> libtransmil_hip_diag.so,
 // loaded by scripts/microbench.py through TRANSMIL_HIP_LIB).  They are named (GemmSel in gemm.hip,
-// NysSel in nystrom.hip) and of two kinds only: the timing-stamp instantiation of a shipped kernel,
+// NysSel in nystrom_bf16.h) and of two kinds only: the timing-stamp instantiation of a shipped kernel,
 // or a forced path between shipped kernels.  The product library has no process-global mutable
 // state: every selector is the constant 0 (the product's own pick), the stamped instantiations
 // are not compiled and no tm_debug_* symbol is exported.

@@ -461,7 +461,7 @@ def nystrom_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdt
             _lib.call("tm_nys_conv_bwd", dt_code, _p(dmerged), _p(merged), _p(v), _p(wconv), nbh, nh, n, _p(dv),
                       _p(d1), _p(work), _p(dwconv_out), _rq(), st)
         # A1 product backward: dq (complete), dkl, dY
-        qpw = 256 if n % 256 == 0 else 32
+        qpw = 256                    # geo.n is a multiple of 256 (Geometry)
         work = pool(_lib.query("tm_nys_a1_bwd_workspace", nbh, n, qpw) // 4)
         with defer_reductions():     # its dk~ and dY slab sums as one launch
             with probe("a1_bwd"):
