@@ -227,6 +227,60 @@ int tm_nys_assemble_q_slab(int dtype, const float* dq, int dq_row, const float* 
 int tm_nys_assemble_q_slab_inplace(const float* dql, const void* slab, int slabs, int nbags, int nh, int n,
                                    float scale, void* dqkv, void* stream);
 
+/* ---- geometry-generic NystromAttention core, fp32 (nystrom_geo.hip) --------
+ * The same stages as the tm_nys_* / tm_pinv_* entry points above for the TransMIL widths other than
+ * 512: (dh, nl) = (dim_head, landmarks) in {(32, 128), (48, 192)} (out_features 256 / 384; TransLayer
+ * builds dim_head = dim / 8, landmarks = dim / 2, code/models/TransMIL.py:26-31).  fp32 operands,
+ * fp32 FMA arithmetic and accumulation; q, k, v [B*h][n][dh] (q pre-scaled), landmarks / W / Y
+ * [B*h][nl][dh], A2 / Z [B*h][nl][nl], merged / dmerged [B][n][h*dh]; n a positive multiple of nl.
+ * Every entry point refuses an unsupported (dh, nl), a bad n and null pointers before any device
+ * work; the *_workspace / *_floats queries return -1 for them.  (64, 256) stays on the entry points
+ * above. */
+int tm_nysg_landmarks(int dh, int nl, const float* q, const float* k, int nbh, int n, float* ql, float* kl,
+                      void* stream);
+long long tm_nysg_a3_workspace(int dh, int nl, int nbh, int n);   /* bytes */
+/* W = softmax(ql k^T) v [B*h][nl][dh] and lse3 [B*h][nl], key-split in blocks of nl keys */
+int tm_nysg_a3_fwd(int dh, int nl, const float* ql, const float* k, const float* v, int nbh, int n, float* work,
+                   float* w, float* lse3, void* stream);
+int tm_nysg_sim2_softmax(int dh, int nl, const float* ql, const float* kl, int nbh, float* a2, void* stream);
+int tm_nysg_softmax_bwd_rows(int dh, int nl, const float* a, const float* da, float* ds, long long rows,
+                             void* stream);
+long long tm_nysg_pinv_saved_floats(int dh, int nl, int nbh, int iters);
+/* as tm_pinv_fwd (prec 0): the abs-sum maxima are taken over ALL bags and heads; iters >= 1 */
+int tm_nysg_pinv_fwd(int dh, int nl, const float* X, int nbh, int iters, float* saved, void* stream);
+long long tm_nysg_pinv_bwd_workspace_floats(int dh, int nl, int nbh);
+int tm_nysg_pinv_bwd(int dh, int nl, const float* X, int nbh, int iters, const float* saved, float* dZ,
+                     float* work, float* dX, void* stream);
+/* C = op(A) B + e1 E1 per head: A [nl][nl] (ta = 1: transposed), B, C, E1 (or NULL) [nl][dh]:
+ * Y = Z W, dW = Z^T dY, dq~ = dS2 k~ + dq~3, dk~ = dS2^T q~ + dk~ */
+int tm_nysg_mm(int dh, int nl, const float* A, int ta, const float* B, const float* E1, float e1, float* C,
+               int nbh, void* stream);
+/* merged = softmax(q kl^T) y + conv33(v) (fp32 [B][n][h*dh]), lse1 [B*h][n] */
+int tm_nysg_a1_fwd(int dh, int nl, const float* q, const float* v, const float* kl, const float* y,
+                   const float* wconv, int nbh, int nh, int n, float* merged, float* lse1, void* stream);
+long long tm_nysg_conv_bwd_workspace(int dh, int nl, int nbags, int nh, int n);   /* bytes */
+int tm_nysg_conv_bwd(int dh, int nl, const float* dmerged, const float* merged, const float* v,
+                     const float* wconv, int nbh, int nh, int n, float* dv, float* d1, float* work,
+                     float* dwconv, tm_reduce_queue* rq, void* stream);
+long long tm_nysg_a1_bwd_workspace(int dh, int nl, int nbh, int n);   /* bytes */
+/* dq (=) [B*h][n][dh]; dkl, dy (=) [B*h][nl][dh] summed from the workspace's slabs (deferred into rq) */
+int tm_nysg_a1_bwd(int dh, int nl, const float* q, const float* dmerged, const float* kl, const float* y,
+                   const float* lse1, const float* d1, int nbh, int nh, int n, float* dq, float* work,
+                   float* dkl, float* dy, tm_reduce_queue* rq, void* stream);
+long long tm_nysg_a3_bwd_workspace(int dh, int nl, int nbh, int n);   /* bytes */
+/* dk (=), dv (+=: it holds the conv backward's dv) [B*h][n][dh]; dql (=) from the slabs;
+ * D = rowsum(dw o w) is computed by the kernel */
+int tm_nysg_a3_bwd(int dh, int nl, const float* ql, const float* dw, const float* w, const float* k,
+                   const float* v, const float* lse3, int nbh, int n, float* dk, float* dv, float* work,
+                   float* dql, tm_reduce_queue* rq, void* stream);
+/* dqkv [B][n][3*h*dh] in `dtype` as tm_nys_assemble_dqkv */
+int tm_nysg_assemble_dqkv(int dh, int nl, int dtype, const float* dq, const float* dql, const float* dk,
+                          const float* dkl, const float* dv, int nbags, int nh, int n, float scale, void* dqkv,
+                          void* stream);
+/* tm_nys_attn_row for this family (fp32 q, k) */
+int tm_nysg_attn_row(int dh, int nl, const float* q, const float* k, const float* ql, const float* kl,
+                     const float* z, const float* lse3, int nbh, int n, int row, float* out, void* stream);
+
 /* ---- exact softmax attention (attention.hip) ------------------------------
  * TransformerMIL's ViT blocks (code/models/_transformer.py:33-43): softmax(q k^T * scale) v, dh = 64,
  * no mask, not causal, no dropout on the probabilities.  q, k, v, out, dout, dqkv are fp32 in memory.

@@ -101,6 +101,25 @@ _SIGS = {
     "tm_nys_assemble_q_slab": (I, [I, P, I, P, P, I, I, I, I, Fl, P, P]),
     "tm_nys_assemble_q_slab_inplace": (I, [P, P, I, I, I, I, Fl, P, P]),
     "tm_nys_attn_row": (I, [I, P, P, P, P, P, P, I, I, I, P, P]),
+    "tm_nysg_landmarks": (I, [I, I, P, P, I, I, P, P, P]),
+    "tm_nysg_a3_workspace": (L, [I, I, I, I]),
+    "tm_nysg_a3_fwd": (I, [I, I, P, P, P, I, I, P, P, P, P]),
+    "tm_nysg_sim2_softmax": (I, [I, I, P, P, I, P, P]),
+    "tm_nysg_softmax_bwd_rows": (I, [I, I, P, P, P, L, P]),
+    "tm_nysg_pinv_saved_floats": (L, [I, I, I, I]),
+    "tm_nysg_pinv_fwd": (I, [I, I, P, I, I, P, P]),
+    "tm_nysg_pinv_bwd_workspace_floats": (L, [I, I, I]),
+    "tm_nysg_pinv_bwd": (I, [I, I, P, I, I, P, P, P, P, P]),
+    "tm_nysg_mm": (I, [I, I, P, I, P, P, Fl, P, I, P]),
+    "tm_nysg_a1_fwd": (I, [I, I, P, P, P, P, P, I, I, I, P, P, P]),
+    "tm_nysg_conv_bwd_workspace": (L, [I, I, I, I, I]),
+    "tm_nysg_conv_bwd": (I, [I, I, P, P, P, P, I, I, I, P, P, P, P, P, P]),
+    "tm_nysg_a1_bwd_workspace": (L, [I, I, I, I]),
+    "tm_nysg_a1_bwd": (I, [I, I, P, P, P, P, P, P, I, I, I, P, P, P, P, P, P]),
+    "tm_nysg_a3_bwd_workspace": (L, [I, I, I, I]),
+    "tm_nysg_a3_bwd": (I, [I, I, P, P, P, P, P, P, I, I, P, P, P, P, P, P]),
+    "tm_nysg_assemble_dqkv": (I, [I, I, I, P, P, P, P, P, I, I, I, Fl, P, P]),
+    "tm_nysg_attn_row": (I, [I, I, P, P, P, P, P, P, I, I, I, P, P]),
     "tm_attn_fwd": (I, [I, P, P, P, I, I, I, L, Fl, P, P, P]),
     "tm_attn_bwd_workspace": (L, [I, I, I]),
     "tm_attn_bwd": (I, [I, P, P, P, P, P, P, I, I, I, L, Fl, P, P, P]),

@@ -30,6 +30,9 @@ DH = 64         # dim_head
 TAPS = 33       # residual conv
 PINV_ITERS = 6
 LN_EPS = 1e-5
+# (dim_head, landmarks) the HIP core runs: 512-wide on the MFMA kernels (both compute modes), the
+# 256- and 384-wide TransMIL geometries on the fp32 tm_nysg_* family (nystrom_geo.hip)
+GEOMETRIES = ((DH, NL), (32, 128), (48, 192))
 QROWS = NL + 32  # rows per bag of tm_cls_q_rows' operands (landmarks, class row, zero rows to 32 | rows)
 # bf16 class-row layer: the q part of to_qkv's backward as two small products (False: the dense q
 # block of dqkv; the equivalence test sets it)
@@ -116,14 +119,16 @@ class Geometry:
     F: int
     D: int
     heads: int
+    dh: int = DH     # dim_head
+    nl: int = NL     # landmarks
 
     def __post_init__(self):
         self.G = int(math.ceil(math.sqrt(self.N)))
         self.add = self.G * self.G - self.N
         self.S = self.G * self.G + 1
-        self.n = ((self.S + NL - 1) // NL) * NL
+        self.n = ((self.S + self.nl - 1) // self.nl) * self.nl
         self.pad = self.n - self.S
-        self.l = self.n // NL
+        self.l = self.n // self.nl
         self.nbh = self.B * self.heads
 
 
@@ -361,7 +366,13 @@ def flush_reductions():
 # ----------------------------------------------------------------------------- NystromAttention core
 def nystrom_core_forward(qkv, geo: Geometry, wconv, tdtype, dt_code, pool, cls_row=None):
     """App. A eq. 4-9 on q, k, v [3, B*h, n, 64] -> merged [B, n, h*64] (T) + saved state.
-    ``cls_row``: only that row of merged (and of the A1 log-sum-exp) is computed (clsrow.hip)."""
+    ``cls_row``: only that row of merged (and of the A1 log-sum-exp) is computed (clsrow.hip).
+    A geometry other than (64, 256) runs the fp32 tm_nysg_* family: q, k, v and merged are fp32
+    in both compute modes (``_nysg_core_forward``)."""
+    if (geo.dh, geo.nl) != (DH, NL):
+        if cls_row is not None:
+            raise NotImplementedError("the class-row layer runs at dim_head=64, num_landmarks=256 only")
+        return _nysg_core_forward(qkv, geo, wconv, pool)
     n, nbh, nh = geo.n, geo.nbh, geo.heads
     q, k, v = qkv[0], qkv[1], qkv[2]
     st = _stream()
@@ -427,7 +438,13 @@ def nystrom_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdt
     """Backward of nystrom_core_forward: returns (dqkv [B, n, 3*h*64] (T), qrows); writes dwconv_out.
     ``cls_row``: dmerged is [B, h*64], the only non-zero row (``cls_row``) of the dense gradient.
     ``xn`` (bf16 class-row layer): the q block of dqkv is NOT written; qrows = (Aq, Xs), the
-    operands of the q part's two small products (tm_cls_q_rows), else qrows = None."""
+    operands of the q part's two small products (tm_cls_q_rows), else qrows = None.
+    A geometry other than (64, 256): dmerged, merged and qkv are fp32 (``_nysg_core_backward``)."""
+    if (geo.dh, geo.nl) != (DH, NL):
+        if cls_row is not None:
+            raise NotImplementedError("the class-row layer runs at dim_head=64, num_landmarks=256 only")
+        return _nysg_core_backward(dmerged, merged, qkv, state, geo, wconv, tdtype, dt_code, pool, dwconv_out,
+                                   scale), None
     n, nbh, nh = geo.n, geo.nbh, geo.heads
     q, k, v = qkv[0], qkv[1], qkv[2]
     st = _stream()
@@ -549,6 +566,99 @@ def nystrom_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdt
     _lib.call("tm_nys_assemble_dqkv", dt_code, _p(dq), _p(dql), _p(dk), _p(dkl), _p(dv), geo.B, nh, n,
               C.c_float(scale), _p(dqkv), st)
     return dqkv, None
+
+
+def _nysg_mm(geo, A, ta, Bm, Cout, E1=None, e1=0.0):
+    """Cout = op(A) Bm + e1 E1 per head: A [nl, nl] (ta: transposed), Bm / Cout / E1 [nl, dh]."""
+    _lib.call("tm_nysg_mm", geo.dh, geo.nl, _p(A), int(ta), _p(Bm), _p(E1), C.c_float(e1), _p(Cout), geo.nbh,
+              _stream())
+
+
+def _nysg_core_forward(qkv, geo: Geometry, wconv, pool):
+    """nystrom_core_forward for the 256- / 384-wide geometries on the fp32 tm_nysg_* family:
+    q, k, v [3, B*h, n, dh] fp32 -> merged [B, n, h*dh] fp32 + the saved state (same keys)."""
+    n, nbh, nh, dh, nl = geo.n, geo.nbh, geo.heads, geo.dh, geo.nl
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    st = _stream()
+    ql = pool(nbh * nl * dh).view(nbh, nl, dh)
+    kl = pool(nbh * nl * dh).view(nbh, nl, dh)
+    with probe("landmarks"):
+        _lib.call("tm_nysg_landmarks", dh, nl, _p(q), _p(k), nbh, n, _p(ql), _p(kl), st)
+    w = pool(nbh * nl * dh).view(nbh, nl, dh)
+    lse3 = pool(nbh * nl)
+    work = pool(_lib.query("tm_nysg_a3_workspace", dh, nl, nbh, n) // 4)
+    with probe("a3_fwd"):
+        _lib.call("tm_nysg_a3_fwd", dh, nl, _p(ql), _p(k), _p(v), nbh, n, _p(work), _p(w), _p(lse3), st)
+    a2 = pool(nbh * nl * nl).view(nbh, nl, nl)
+    mat = nbh * nl * nl
+    saved = pool(_lib.query("tm_nysg_pinv_saved_floats", dh, nl, nbh, PINV_ITERS))
+    with probe("pinv_fwd"):
+        _lib.call("tm_nysg_sim2_softmax", dh, nl, _p(ql), _p(kl), nbh, _p(a2), st)
+        _lib.call("tm_nysg_pinv_fwd", dh, nl, _p(a2), nbh, PINV_ITERS, _p(saved), st)
+    z = saved[PINV_ITERS * mat:(PINV_ITERS + 1) * mat].view(nbh, nl, nl)
+    y = pool(nbh * nl * dh).view(nbh, nl, dh)
+    _nysg_mm(geo, z, 0, w, y)
+    merged = pool(geo.B * n * nh * dh).view(geo.B, n, nh * dh)
+    lse1 = pool(nbh * n)
+    with probe("a1_fwd"):
+        _lib.call("tm_nysg_a1_fwd", dh, nl, _p(q), _p(v), _p(kl), _p(y), _p(wconv), nbh, nh, n, _p(merged),
+                  _p(lse1), st)
+    state = dict(ql=ql, kl=kl, ql_t=ql, kl_t=kl, a2=a2, a2s=None, pinv=saved, z=z, w=w, lse3=lse3, y=y, y_t=y,
+                 lse1=lse1)
+    return merged, state
+
+
+def _nysg_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdtype, dt_code, pool, dwconv_out, scale):
+    """Backward of _nysg_core_forward: dmerged, merged, qkv fp32 -> dqkv [B, n, 3*h*dh] (T);
+    writes dwconv_out."""
+    n, nbh, nh, dh, nl = geo.n, geo.nbh, geo.heads, geo.dh, geo.nl
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    st = _stream()
+    mat = nbh * nl * nl
+    ql, kl, w, z, y, a2 = state["ql"], state["kl"], state["w"], state["z"], state["y"], state["a2"]
+    # conv33 backward + D1
+    dv = pool(nbh * n * dh)
+    d1 = pool(nbh * n)
+    with defer_reductions(), probe("conv_bwd"):
+        work = pool(_lib.query("tm_nysg_conv_bwd_workspace", dh, nl, geo.B, nh, n) // 4)
+        _lib.call("tm_nysg_conv_bwd", dh, nl, _p(dmerged), _p(merged), _p(v), _p(wconv), nbh, nh, n, _p(dv), _p(d1),
+                  _p(work), _p(dwconv_out), _rq(), st)
+    # A1 product backward: dq (complete), dk~, dY
+    dq = pool(nbh * n * dh)
+    dkl = pool(nbh * nl * dh).view(nbh, nl, dh)
+    dy = pool(nbh * nl * dh).view(nbh, nl, dh)
+    work = pool(_lib.query("tm_nysg_a1_bwd_workspace", dh, nl, nbh, n) // 4)
+    with defer_reductions(), probe("a1_bwd"):
+        _lib.call("tm_nysg_a1_bwd", dh, nl, _p(q), _p(dmerged), _p(kl), _p(y), _p(state["lse1"]), _p(d1), nbh, nh, n,
+                  _p(dq), _p(work), _p(dkl), _p(dy), _rq(), st)
+    flush_reductions()
+    # Y = Z W: dZ = dY W^T (tm_bmm, K = dh), dW = Z^T dY
+    dz = pool(mat).view(nbh, nl, nl)
+    bmm([bmm_job(dy, 0, w, 1, dz, nl, nl, dh)], nbh, 0)
+    dw = pool(nbh * nl * dh).view(nbh, nl, dh)
+    _nysg_mm(geo, z, 1, dy, dw)
+    # A3 product backward: dk (=), dv (+=), dq~3 (=)
+    dk = pool(nbh * n * dh)
+    dql3 = pool(nbh * nl * dh).view(nbh, nl, dh)
+    work3 = pool(_lib.query("tm_nysg_a3_bwd_workspace", dh, nl, nbh, n) // 4)
+    with probe("a3_bwd"):
+        _lib.call("tm_nysg_a3_bwd", dh, nl, _p(ql), _p(dw), _p(w), _p(k), _p(v), _p(state["lse3"]), nbh, n, _p(dk),
+                  _p(dv), _p(work3), _p(dql3), _rq(), st)
+    # pseudo-inverse backward -> dA2, then the row-softmax backward
+    da2 = pool(mat).view(nbh, nl, nl)
+    ds2 = pool(mat).view(nbh, nl, nl)
+    pwork = pool(_lib.query("tm_nysg_pinv_bwd_workspace_floats", dh, nl, nbh))
+    with probe("pinv_bwd"):
+        _lib.call("tm_nysg_pinv_bwd", dh, nl, _p(a2), nbh, PINV_ITERS, _p(state["pinv"]), _p(dz), _p(pwork), _p(da2),
+                  st)
+        _lib.call("tm_nysg_softmax_bwd_rows", dh, nl, _p(a2), _p(da2), _p(ds2), nbh * nl, st)
+    dql = pool(nbh * nl * dh).view(nbh, nl, dh)
+    _nysg_mm(geo, ds2, 0, kl, dql, E1=dql3, e1=1.0)
+    _nysg_mm(geo, ds2, 1, ql, dkl, E1=dkl, e1=1.0)
+    dqkv = pool(geo.B * n * 3 * nh * dh, tdtype).view(geo.B, n, 3 * nh * dh)
+    _lib.call("tm_nysg_assemble_dqkv", dh, nl, dt_code, _p(dq), _p(dql), _p(dk), _p(dkl), _p(dv), geo.B, nh, n,
+              C.c_float(scale), _p(dqkv), st)
+    return dqkv
 
 
 # ----------------------------------------------------------------------------- TransLayer
@@ -1015,28 +1125,39 @@ class NystromEngine:
         _lib.call("tm_cast_f32", self.dt_code, _p(w.contiguous()), _p(out), w.numel(), _stream())
         return out.view(w.shape)
 
-    def forward(self, x, wqkv, wo, bo, wconv, heads, drop_p=0.0, seed=0, seed_dev=None):
+    def forward(self, x, wqkv, wo, bo, wconv, heads, drop_p=0.0, seed=0, seed_dev=None, dim_head=DH,
+                num_landmarks=NL):
         B, S, D = x.shape
+        dh, nl = dim_head, num_landmarks
+        if (dh, nl) not in GEOMETRIES or D != heads * dh:
+            raise NotImplementedError(f"HIP NystromAttention: (dim_head, num_landmarks) must be one of {GEOMETRIES} "
+                                      f"with dim == heads * dim_head (got {(dh, nl)}, dim={D}, heads={heads})")
+        generic = (dh, nl) != (DH, NL)   # the fp32 tm_nysg_* core: q, k, v and merged stay fp32
         pool = Pool(x.device)
-        geo = Geometry(B, max(S - 1, 1), D, D, heads)
+        geo = Geometry(B, max(S - 1, 1), D, D, heads, dh, nl)
         geo.S = S
-        geo.n = ((S + NL - 1) // NL) * NL
+        geo.n = ((S + nl - 1) // nl) * nl
         geo.pad = geo.n - S
-        geo.l = geo.n // NL
+        geo.l = geo.n // nl
         n, pad = geo.n, geo.pad
         xc = x.reshape(B * S, D).contiguous()
         xp = pool(B * n * D, self.tdtype).view(B, n, D)
         _lib.call("tm_pad_rows", self.dt_code, _p(xc), B, S, n, pad, D, _p(xp), _stream())
         wqkv_t, wo_t = self._cast(wqkv, pool), self._cast(wo, pool)
-        qkv = pool(3 * geo.nbh * n * DH, self.tdtype).view(3, geo.nbh, n, DH)
+        qdtype = torch.float32 if generic else self.tdtype
+        qkv = pool(3 * geo.nbh * n * dh, qdtype).view(3, geo.nbh, n, dh)
         gemm(xp, wqkv_t, qkv, B * n, 3 * D, D, lda=D, ldb=D, ldc=0, dtype=self.dt_code,
-             qkv=(B, heads, DH, n, DH ** -0.5))
+             c_dtype=F32 if generic else None, qkv=(B, heads, dh, n, dh ** -0.5))
         merged, state = nystrom_core_forward(qkv, geo, wconv.contiguous(), self.tdtype, self.dt_code, pool)
+        merged_core = merged
+        if generic and self.dt_code != F32:   # the to_out GEMM's bf16 operand
+            merged = pool(B * n * D, self.tdtype).view(B, n, D)
+            _lib.call("tm_cast_f32", self.dt_code, _p(merged_core), _p(merged), B * n * D, _stream())
         out = torch.empty(B, S, D, dtype=torch.float32, device=x.device)
         gemm(merged, wo_t, out, B * n, D, D, lda=D, ldb=D, ldc=D, dtype=self.dt_code, c_dtype=F32,
              bias=bo, drop_p=drop_p, seed=seed, seed_ptr=seed_dev, rowmap=(n, pad, S, 0, 0, 0))
-        ctx = dict(geo=geo, xp=xp, qkv=qkv, merged=merged, core=state, wqkv_t=wqkv_t, wo_t=wo_t,
-                   wconv=wconv.contiguous(), drop_p=drop_p, seed=seed, seed_dev=seed_dev)
+        ctx = dict(geo=geo, xp=xp, qkv=qkv, merged=merged, merged_core=merged_core, core=state, wqkv_t=wqkv_t,
+                   wo_t=wo_t, wconv=wconv.contiguous(), drop_p=drop_p, seed=seed, seed_dev=seed_dev)
         return out, ctx
 
     def backward(self, dout, ctx):
@@ -1055,11 +1176,13 @@ class NystromEngine:
         dbo = torch.empty(D, dtype=torch.float32, device=dout.device)
         weight_grad(dpad, ctx["merged"], dwo, D, D, B * n, ldy=D, ldx=D, dtype=self.dt_code, work_pool=pool,
                     bias_out=dbo)
-        dmerged = pool(B * n * D, self.tdtype).view(B, n, D)
-        gemm(dpad, ctx["wo_t"], dmerged, B * n, D, D, lda=D, ldb=D, ldc=D, b_kn=1, dtype=self.dt_code)
+        generic = (geo.dh, geo.nl) != (DH, NL)   # fp32 core: dmerged in fp32 from the same GEMM
+        dmerged = pool(B * n * D, torch.float32 if generic else self.tdtype).view(B, n, D)
+        gemm(dpad, ctx["wo_t"], dmerged, B * n, D, D, lda=D, ldb=D, ldc=D, b_kn=1, dtype=self.dt_code,
+             c_dtype=F32 if generic else None)
         dwconv = torch.empty_like(ctx["wconv"], dtype=torch.float32)
-        dqkv, _ = nystrom_core_backward(dmerged, ctx["merged"], ctx["qkv"], ctx["core"], geo, ctx["wconv"],
-                                        self.tdtype, self.dt_code, pool, dwconv, DH ** -0.5)
+        dqkv, _ = nystrom_core_backward(dmerged, ctx["merged_core"], ctx["qkv"], ctx["core"], geo, ctx["wconv"],
+                                        self.tdtype, self.dt_code, pool, dwconv, geo.dh ** -0.5)
         dwqkv = torch.empty(3 * D, D, dtype=torch.float32, device=dout.device)
         weight_grad(dqkv, ctx["xp"], dwqkv, 3 * D, D, B * n, ldy=3 * D, ldx=D, dtype=self.dt_code, work_pool=pool)
         dx = torch.empty(B, S, D, dtype=torch.float32, device=dout.device)

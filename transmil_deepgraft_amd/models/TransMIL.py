@@ -20,7 +20,13 @@ branch ``Linear(2048,1024) + GELU + LayerNorm(1024) + Linear(1024,512) + GELU``
 (:100-111, the RetCCL-feature config), and the 768 branch (:122-126: two Linear+GELU on the HIP
 GEMM with Dropout and HIP LayerNorms, then the engine's pre-embedded-input mode).  The 1024
 branch raises, as the reference's does (its LayerNorm(out_features) meets a 1024-wide input,
-:117-121).  ``dim_head`` is fixed at 64 by TransLayer (dim // 8, dim = 512).
+:117-121).
+
+``out_features`` 512, 256 and 384 run (every width a reference config uses): TransLayer builds
+``dim_head = dim // 8`` and ``num_landmarks = dim // 2``.  The fused engine and its class-row kernels
+are 512-wide; at 256 and 384 ``forward`` runs the module-by-module path by itself (every op a HIP
+kernel, the NystromAttention core on the fp32 ``tm_nysg_*`` family), ``forward_ce`` returns
+``None`` (the caller computes the loss from ``forward``) and no gradient bucket is attached.
 """
 from __future__ import annotations
 
@@ -193,10 +199,16 @@ class TransMIL(nn.Module):
             return [p0, [p for _, p in rest]]
         return [p0, [p for n, p in rest if n.startswith("layer1.")], [p for n, p in rest if not n.startswith("layer1.")]]
 
+    def _fused_width(self):
+        """The fused engine (and its class-row kernels) is 512-wide; the other widths run module by
+        module."""
+        return self.norm.weight.shape[0] == 512
+
     def attach_grad_bucket(self, bucket):
         """Route the fused backward's parameter gradients into ``bucket`` (interface.GradBucket).
-        Not with a pre-embedded input: its _fc1 gradients come later, from autograd."""
-        self._grad_bucket = None if self._fc1_layout() is FC1_EMBED else bucket
+        Not with a pre-embedded input: its _fc1 gradients come later, from autograd; not at
+        out_features 256 / 384: there is no fused backward to write into it."""
+        self._grad_bucket = None if self._fc1_layout() is FC1_EMBED or not self._fused_width() else bucket
 
     def _hooked(self):
         """A forward / backward hook on any submodule (GradCAM on model.norm or
@@ -263,9 +275,10 @@ class TransMIL(nn.Module):
             raise RuntimeError("TransMIL (HIP) needs a GPU tensor: there is no CPU path")
         layout = self._fc1_layout()
         x = x.float().contiguous()             # :174
-        if not self.fused or self._hooked() or x.requires_grad:
-            # hooks, or a gradient w.r.t. the input (feature saliency): the module-by-module path,
-            # whose ops also return dL/dx; the fused node returns parameter gradients only
+        if not self.fused or not self._fused_width() or self._hooked() or x.requires_grad:
+            # hooks, a gradient w.r.t. the input (feature saliency) or out_features 256 / 384: the
+            # module-by-module path, whose ops also return dL/dx; the fused node is 512-wide and
+            # returns parameter gradients only
             return self._forward_modules(x, return_attn)
         if layout is FC1_EMBED:
             x = self._pre_embed(x).contiguous()
@@ -276,7 +289,10 @@ class TransMIL(nn.Module):
         Y_prob / Y_hat / the per-class count-correct (code/models/model_interface.py:333-356) on
         the fused path, the loss computed in the head's launch: returns (logits, loss, Y_prob,
         Y_hat), or None where the fused path does not apply (hooks, input gradients,
-        ``fused = False``) -- the caller then runs ``forward`` and the loss itself."""
+        ``fused = False``, out_features 256 / 384) -- the caller then runs ``forward`` and the loss
+        itself."""
+        if not self._fused_width():
+            return None
         if x.dim() > 3:
             x = x.squeeze(0)
         elif x.dim() == 2:

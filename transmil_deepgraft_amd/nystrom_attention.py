@@ -8,10 +8,14 @@ num_landmarks=256, pinv_iterations=6, residual=True, dropout=0.7)``
 (``to_qkv``, ``to_out.0``, ``res_conv``) and ``forward(x, mask=None,
 return_attn=False)`` match the package, so state_dicts load unchanged.
 
-Supported geometry on the HIP path: ``dim_head == 64``, ``num_landmarks ==
-256``, ``residual=True`` with the 33-tap conv, ``mask=None`` (every reference
-call site).  Anything else raises ``NotImplementedError`` -- there is no CPU
-or eager-PyTorch fallback.
+Supported geometry on the HIP path: ``(dim_head, num_landmarks)`` in ``{(64, 256),
+(32, 128), (48, 192)}`` -- what ``TransLayer`` builds for ``out_features`` 512, 256 and
+384 (``dim // 8``, ``dim // 2``) -- with ``dim == heads * dim_head``, ``pinv_iterations=6``,
+``residual=True`` with the 33-tap conv and ``mask=None`` (every reference call site).
+``(64, 256)`` runs the MFMA kernels in both compute modes; the other two run the fp32
+``tm_nysg_*`` core (``csrc/nystrom_geo.hip``) in both modes, the bf16 mode keeping only the
+``to_qkv`` / ``to_out`` projections and their backward products on the bf16 GEMMs.  Anything
+else raises ``NotImplementedError`` -- there is no CPU or eager-PyTorch fallback.
 
 ``return_attn=True`` returns an :class:`AttentionMap` -- ``attn1 @ attn2_inv @ attn3``
 ([B, h, n, n], SURVEY.md App. A eq. 11) held as the forward's factors.  Indexing one
@@ -28,7 +32,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import BF16, F32
-from .engine import NystromEngine, NL, DH, _p, _stream
+from .engine import NystromEngine, GEOMETRIES, NL, DH, _p, _stream
 
 
 def _check_dtype(dtype):
@@ -39,9 +43,11 @@ def _check_dtype(dtype):
 
 class _NystromFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, heads, drop_p, seed_dev, holder, x, wqkv, wo, bo, wconv):
+    def forward(ctx, engine, geometry, drop_p, seed_dev, holder, x, wqkv, wo, bo, wconv):
+        heads, dim_head, num_landmarks = geometry
         with torch.cuda.device(x.device):
-            out, c = engine.forward(x, wqkv, wo, bo, wconv, heads, drop_p, 0x51ED27, seed_dev)
+            out, c = engine.forward(x, wqkv, wo, bo, wconv, heads, drop_p, 0x51ED27, seed_dev,
+                                    dim_head=dim_head, num_landmarks=num_landmarks)
         ctx.engine, ctx.c = engine, c
         if holder is not None:
             holder["c"] = c
@@ -79,11 +85,13 @@ class NystromAttention(nn.Module):
     def _supported(self, mask):
         if mask is not None:
             raise NotImplementedError("HIP NystromAttention: mask is not supported (no reference call site uses it)")
-        if (self.dim_head, self.num_landmarks, self.pinv_iterations) != (DH, NL, 6) or not self.residual \
-                or self.residual_conv_kernel != 33:
+        if (self.dim_head, self.num_landmarks) not in GEOMETRIES or self.pinv_iterations != 6 \
+                or not self.residual or self.residual_conv_kernel != 33:
             raise NotImplementedError(
-                "HIP NystromAttention supports dim_head=64, num_landmarks=256, pinv_iterations=6, "
-                "residual=True, residual_conv_kernel=33 (the TransMIL configuration)")
+                "HIP NystromAttention supports (dim_head, num_landmarks) in "
+                f"{{{', '.join(str(g) for g in GEOMETRIES)}}} with pinv_iterations=6, residual=True, "
+                "residual_conv_kernel=33 (the TransMIL configurations at out_features 512, 256, 384); got "
+                f"dim_head={self.dim_head}, num_landmarks={self.num_landmarks}")
 
     def forward(self, x, mask=None, return_attn=False):
         self._supported(mask)
@@ -96,7 +104,8 @@ class NystromAttention(nn.Module):
             self._dropout_counter.add_(1)
             seed_dev = self._dropout_counter.clone()
         holder = {} if return_attn else None
-        out = _NystromFn.apply(engine, self.heads, drop_p, seed_dev, holder, x.float(), self.to_qkv.weight,
+        out = _NystromFn.apply(engine, (self.heads, self.dim_head, self.num_landmarks), drop_p, seed_dev, holder,
+                               x.float(), self.to_qkv.weight,
                                self.to_out[0].weight, self.to_out[0].bias, self.res_conv.weight)
         if return_attn:   # the factors of THIS forward (the reference returns attn of the same call)
             return out, AttentionMap(holder["c"]["qkv"], holder["c"]["core"], self.heads)
@@ -123,6 +132,11 @@ def attention_row(qkv, core, heads, row):
         raise IndexError(f"attention row {row} out of range for n = {n}")
     row %= n
     out = torch.empty(nbh, n, device=q.device, dtype=torch.float32)
+    dh, nl = q.shape[2], core["ql"].shape[1]
+    if (dh, nl) != (DH, NL):     # the fp32 family (its q, k are fp32 in both compute modes)
+        _lib.call("tm_nysg_attn_row", dh, nl, _p(q), _p(k), _p(core["ql"]), _p(core["kl"]), _p(core["z"]),
+                  _p(core["lse3"]), nbh, n, row, _p(out), _stream())
+        return out.view(-1, heads, n)
     _lib.call("tm_nys_attn_row", BF16 if q.dtype == torch.bfloat16 else F32, _p(q), _p(k), _p(core["ql"]),
               _p(core["kl"]), _p(core["z"]), _p(core["lse3"]), nbh, n, row, _p(out), _stream())
     return out.view(-1, heads, n)
