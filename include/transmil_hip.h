@@ -478,6 +478,17 @@ int tm_conv1x1(int dtype, const void* x, const void* w, const void* bias, const 
 int tm_conv1x1_tune(int dtype, const void* x, const void* w, const void* bias, const void* residual, void* y,
                     long long rows, int cin, int cout, int relu, void* workspace, long long ws_bytes,
                     void* stream);
+/* ResNet-18 BasicBlock 3x3 convolution (pad 1, stride 1 or 2; BN folded into w / bias) over
+ * channels-last activations, a hand-written implicit GEMM on the MFMA units (conv3x3.hip):
+ * y[n, ho, wo, cout] = act(conv3x3(x[n, h, wd, cin], w) (+ bias[cout]) (+ residual[n, ho, wo, cout])),
+ * ho = (h - 1) / stride + 1, wo = (wd - 1) / stride + 1, act = ReLU when relu != 0.
+ * w is [cout][3][3][cin] (a [cout, cin, 3, 3] tensor contiguous in channels_last).  dtype TM_BF16
+ * (bf16 MFMA, fp32 accumulation, one rounding) or TM_F32 (f32 MFMA) for x, w, bias, residual, y.
+ * cin, cout multiples of 64 up to 512; h, wd in 1..32768; n >= 1; x and y addressed with 64-bit
+ * offsets (no 2^31 limit); every pointer 16-byte aligned; bias / residual may be NULL; y must not
+ * alias x.  Bitwise reproducible (no atomics).  Every refusal's message begins "conv3x3:". */
+int tm_conv3x3(int dtype, const void* x, const void* w, const void* bias, const void* residual, void* y,
+               long long n, int h, int wd, int cin, int cout, int stride, int relu, void* stream);
 /* Train-mode BatchNorm2d over a channels-last activation given as npieces (1..64) row pieces
  * xs[p] of [rows[p], C] (host arrays; C a power of two, 8..2048; nn.BatchNorm2d.forward in
  * training, code/models/ResNet.py:95-117 under model.train()): batch statistics over all pieces

@@ -11,6 +11,13 @@ sample (oracle/encoder_ref.py on ``--cpu-tiles`` tiles, extrapolated per tile to
 TransMIL(2048) oracle fwd + CE + bwd + RAdam step at N measured whole).
 
     python scripts/bench_c5.py [--n 4096] [--steps 20] [--warmup 3] [--encoder-mode train|eval] [--graph]
+
+``--backbone resnet18`` runs the reference's default image configuration instead: the frozen
+ResNet-18 (3x3 convolutions on the hand-written tm_conv3x3 kernel) with its 512 -> 512 fc ->
+TransMIL(2, 512).  ``--compare-library R`` then also times the same encoder with its 3x3
+convolutions routed through the library (MIOpen convolution + tm_bias_act, residual add + ReLU as
+torch passes), R rounds alternating with the hand-written kernel; the route exists in this script
+only.
 """
 from __future__ import annotations
 
@@ -27,6 +34,24 @@ sys.path.insert(0, ROOT)
 
 BF16_PEAK_TFS = 2500.0
 R50_GFLOP_PER_TILE = 4.09   # ResNet-50 forward at 224x224, multiply-adds x 2 (conv + fc-free)
+R18_GFLOP_PER_TILE = 3.63   # ResNet-18 forward at 224x224, multiply-adds x 2 (3.35 of them 3x3 convolutions)
+
+
+def library_conv3x3(x, w, b, stride, relu, residual=None):
+    """encoder._conv3x3's contract on the library route: MIOpen convolution, then the bias / ReLU
+    pass (tm_bias_act) and, for a block's second convolution, the residual add + ReLU."""
+    from transmil_deepgraft_amd import encoder as E
+    y = E._cl(E._lib_conv2d(x, w, None, stride=stride, padding=1))
+    if residual is not None:
+        if b is not None:
+            E._bias_act_(y, b, relu=False)
+        y.add_(residual)
+        return y.relu_() if relu else y
+    if b is not None:
+        E._bias_act_(y, b, relu=relu)
+    elif relu:
+        y.relu_()
+    return y
 
 
 def timed(fn, steps):
@@ -56,17 +81,23 @@ def main():
     # (profiles/r04p_c5_find.jsonl); --no-benchmark keeps MIOpen's immediate-mode heuristics
     ap.add_argument("--benchmark", action=argparse.BooleanOptionalAction, default=True,
                     help="torch.backends.cudnn.benchmark (MIOpen find)")
+    ap.add_argument("--backbone", default="retccl", choices=["retccl", "resnet18"])
+    ap.add_argument("--compare-library", type=int, default=0, metavar="ROUNDS",
+                    help="resnet18: also time the encoder with library 3x3 convolutions, alternating ROUNDS times")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = a.benchmark
-    from transmil_deepgraft_amd.encoder import ImageBagModel, retccl_resnet50
+    from transmil_deepgraft_amd import encoder as encoder_module
+    from transmil_deepgraft_amd.encoder import ImageBagModel, resnet18, retccl_resnet50
     from transmil_deepgraft_amd.interface import GradAllReduce, TransMILTask
     from transmil_deepgraft_amd.models import TransMIL
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
-    enc = retccl_resnet50(chunk=a.chunk).to(dev).set_compute_dtype(torch.bfloat16)
+    r18 = a.backbone == "resnet18"
+    width, gflop = (512, R18_GFLOP_PER_TILE) if r18 else (2048, R50_GFLOP_PER_TILE)
+    enc = (resnet18 if r18 else retccl_resnet50)(chunk=a.chunk).to(dev).set_compute_dtype(torch.bfloat16)
     enc.channels_last = a.layout == "nhwc"
     enc.train(a.encoder_mode == "train")
-    mil = TransMIL(2, 2048, 512).to(dev).train()
+    mil = TransMIL(2, width, 512).to(dev).train()
     model = ImageBagModel(enc, mil)
     task = TransMILTask(mil)
     opt = task.configure_optimizers()[0][0]
@@ -106,29 +137,49 @@ def main():
         opt.step()
         opt.zero_grad(set_to_none=True)
     t_mil = timed(mil_step, a.steps)
-    enc_tfs = R50_GFLOP_PER_TILE * a.n / t_enc / 1e3
-    cpu = cpu_baseline(a, enc, mil) if a.cpu_tiles > 0 else None
+    enc_tfs = gflop * a.n / t_enc / 1e3
+    # the CPU oracle of the encoder is the ResNet-50's (oracle/encoder_ref.py): none for resnet18
+    cpu = cpu_baseline(a, enc, mil) if a.cpu_tiles > 0 and not r18 else None
+    library = None
+    if r18 and a.compare_library > 0:
+        hand = encoder_module._conv3x3
+        ts = {"hand": [], "library": []}
+        with torch.no_grad():
+            for route, fn in (("library", library_conv3x3), ("hand", hand)):     # warm both (MIOpen find)
+                encoder_module._conv3x3 = fn
+                enc(tiles[0])
+            for _ in range(a.compare_library):
+                for route, fn in (("hand", hand), ("library", library_conv3x3)):
+                    encoder_module._conv3x3 = fn
+                    ts[route].append(timed(lambda: enc(tiles[0]), a.steps) * 1e3)
+        encoder_module._conv3x3 = hand
+        library = {"rounds": a.compare_library, "steps_per_round": a.steps,
+                   "encoder_ms_hand": [round(t, 3) for t in ts["hand"]],
+                   "encoder_ms_library": [round(t, 3) for t in ts["library"]],
+                   "note": "same process, alternating; library = MIOpen 3x3 + tm_bias_act (+ torch add / ReLU)"}
+    name = "ResNet-18 encoder (fc 512) + TransMIL(512)" if r18 else "RetCCL ResNet-50 encoder + TransMIL(2048)"
     print(json.dumps({
-        "metric": f"slides/sec (fwd+bwd) end-to-end, RetCCL ResNet-50 encoder + TransMIL(2048), N={a.n} tiles",
+        "metric": f"slides/sec (fwd+bwd) end-to-end, {name}, N={a.n} tiles",
         "value": round(1.0 / t_step, 3), "unit": "slides/sec", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(t_step * 1e3, 3), "higher_is_better": True, "dtype": "bf16",
         "data": "synthetic (randn tiles resident in HBM, random-init weights)",
-        "config": {"workload": f"C5: 1 slide x {a.n} tiles 3x224x224 -> ResNet-50 (frozen, BN "
+        "config": {"workload": f"C5: 1 slide x {a.n} tiles 3x224x224 -> {'ResNet-18' if r18 else 'ResNet-50'} (frozen, BN "
                                f"{'batch stats' if a.encoder_mode == 'train' else 'folded'}) -> TransMIL 2-class",
                    "execution": "hipGraph" if a.graph else "eager", "chunk": a.chunk, "layout": a.layout,
-                   "miopen_find": a.benchmark},
+                   "miopen_find": a.benchmark, "backbone": a.backbone},
         "encoder": {"ms": round(t_enc * 1e3, 3), "tiles_per_s": round(a.n / t_enc, 1),
                     "achieved_tfs": round(enc_tfs, 1), "peak_tfs": BF16_PEAK_TFS,
                     "frac": round(enc_tfs / BF16_PEAK_TFS, 4), "mode": a.encoder_mode,
-                    "flops_note": f"{R50_GFLOP_PER_TILE} GFLOP per 224x224 tile (ResNet-50 forward)"},
+                    "flops_note": f"{gflop} GFLOP per 224x224 tile ({'ResNet-18' if r18 else 'ResNet-50'} forward)"},
         "mil_ms": round(t_mil * 1e3, 3),
         "roofline": {"bound": "mfma", "achieved": round(enc_tfs, 1), "peak": BF16_PEAK_TFS, "unit": "TFLOP/s",
                      "frac": round(enc_tfs / BF16_PEAK_TFS, 4), "traffic": None,
                      "kernel": f"encoder ({a.encoder_mode} BN): hand-written stem (conv + BN + ReLU + pool, "
-                               "tm_stem_*), MIOpen / CK 3x3 convolutions, hipBLASLt 1x1 GEMMs (tm_conv1x1), "
-                               "HIP BatchNorm / bias passes",
-                     "algorithmic_flops": int(R50_GFLOP_PER_TILE * 1e9 * a.n), "ms": round(t_enc * 1e3, 3)},
-        "cpu_baseline": cpu,
+                               "tm_stem_*), " + ("hand-written 3x3 implicit-GEMM convolutions (tm_conv3x3), " if r18
+                                                 else "MIOpen / CK 3x3 convolutions, ") +
+                               "hipBLASLt 1x1 GEMMs (tm_conv1x1), HIP BatchNorm / bias passes",
+                     "algorithmic_flops": int(gflop * 1e9 * a.n), "ms": round(t_enc * 1e3, 3)},
+        "cpu_baseline": cpu, "library_comparison": library,
     }), flush=True)
 
 

@@ -9,7 +9,9 @@ code/utils/utils.py:63-66, but with yaml.SafeLoader) and maps the keys `train.py
   follows ``Data.feature_extractor`` as train.py:392-397 sets it (retccl 2048, histoencoder 384,
   ctranspath 784), default 1024 as ModelInterface's default.
 * ``Model.backbone`` -> ``features`` runs on bags of features; ``retccl`` wraps the model in the
-  on-GPU RetCCL encoder (``encoder.ImageBagModel``, model_interface.py:237-247, 300-316).
+  on-GPU RetCCL encoder (``encoder.ImageBagModel``, model_interface.py:237-247, 300-316) and
+  ``resnet18`` in the frozen ResNet-18 with its trainable 512 -> 512 ``fc`` (:226-234; the MIL
+  model then takes 512 features).
 * ``General.precision`` -> ``compute_dtype``: the reference's 16 / '16-mixed' (fp16 autocast)
   and 'bf16' / 'bf16-mixed' run the bf16 MFMA mode, 32 / '32-true' the fp32 parity mode.
 * ``Optimizer.opt / lr / weight_decay``, ``Loss.base_loss`` -> ``TransMILTask``;
@@ -42,6 +44,14 @@ def read_yaml(path) -> AttrDict:
 
 
 _FEATURE_WIDTH = {"retccl": 2048, "histoencoder": 384, "ctranspath": 784}
+_RESNET18_WIDTH = 512      # model_ft.fc = nn.Linear(512, 512) (model_interface.py:159, 234)
+
+
+def _image_backbone(cfg):
+    """The on-GPU tile encoder the config asks for (None: bags of features)."""
+    if (cfg.Data or {}).get("feature_extractor") is not None:
+        return None
+    return cfg.Model.backbone if cfg.Model.backbone in ("retccl", "resnet18") else None
 
 
 def compute_dtype_for(precision) -> torch.dtype:
@@ -58,13 +68,20 @@ def in_features_of(cfg) -> int:
     fe = (cfg.Data or {}).get("feature_extractor") if cfg.Data else None
     if fe in _FEATURE_WIDTH:                                   # code/train.py:392-397
         return _FEATURE_WIDTH[fe]
+    if _image_backbone(cfg) == "resnet18":
+        given = cfg.Model.in_features
+        if given is not None and int(given) != _RESNET18_WIDTH:
+            raise ValueError(f"Model.in_features {given} does not match backbone resnet18, whose output "
+                             f"(fc = Linear(512, 512)) is {_RESNET18_WIDTH} wide")
+        return _RESNET18_WIDTH
     return int(cfg.Model.in_features or 1024)
 
 
 def build_model(cfg, device="cuda"):
     """``models.{Model.name}(n_classes, in_features, out_features)`` on the device, in the compute
-    dtype of ``General.precision``; wrapped in the RetCCL encoder for ``backbone: retccl`` on
-    images (``Model.backbone == 'features'`` keeps feature bags)."""
+    dtype of ``General.precision``; wrapped in the RetCCL encoder for ``backbone: retccl`` and in
+    the ResNet-18 encoder for ``backbone: resnet18`` on images (``Model.backbone == 'features'``
+    keeps feature bags)."""
     from . import models
     name = cfg.Model.name
     if not hasattr(models, name):
@@ -80,9 +97,10 @@ def build_model(cfg, device="cuda"):
     dtype = compute_dtype_for(cfg.General.precision if cfg.General else None)
     if hasattr(model, "set_compute_dtype"):
         model.set_compute_dtype(dtype)
-    if cfg.Model.backbone == "retccl" and (cfg.Data or {}).get("feature_extractor") is None:
-        from .encoder import ImageBagModel, retccl_resnet50
-        enc = retccl_resnet50().to(device).set_compute_dtype(dtype)
+    backbone = _image_backbone(cfg)
+    if backbone is not None:
+        from .encoder import ImageBagModel, resnet18, retccl_resnet50
+        enc = (retccl_resnet50 if backbone == "retccl" else resnet18)().to(device).set_compute_dtype(dtype)
         model = ImageBagModel(enc, model)
     return model
 

@@ -30,6 +30,12 @@ Same module / parameter / buffer names as code/models/ResNet.py (ResNet :130-277
   bag is 3.3 G elements at the stem output, and MIOpen's implicit-GEMM NHWC kernels wrap 32-bit
   offsets there: wrong outputs measured, see LIB_MAX_BYTES): every path runs on pieces of at most
   ``max_tiles_per_call()`` tiles or refuses the call.
+
+``ResNet18`` is the ``backbone: resnet18`` encoder of the reference's default configs
+(model_interface.py:226-234): torchvision's layout, frozen body, trainable ``fc = Linear(512, 512)``.
+It shares the controls, the stem and the forward scaffolding above (``_FrozenTileEncoder``); its 3x3
+convolutions -- all of its BasicBlocks -- run on the hand-written implicit-GEMM kernel
+(csrc/conv3x3.hip, 64-bit addressing) instead of the library.
 """
 from __future__ import annotations
 
@@ -104,6 +110,28 @@ def _conv1x1_gemm(x, w, b, relu, residual=None):
         _lib.call("tm_conv1x1_tune", *args)
         _TUNED.add(key)
     _lib.call("tm_conv1x1", *args)
+    return y
+
+
+def _conv3x3(x, w, b, stride, relu, residual=None):
+    """3x3 convolution (pad 1, stride 1 / 2; BN folded or bias-free) over a channels-last tensor on
+    the hand-written implicit-GEMM kernel with its bias (+ residual) (+ ReLU) epilogue (tm_conv3x3).
+    64-bit addressing: no tile limit per call."""
+    from . import _lib
+    from .engine import _p, _stream
+    cl = torch.channels_last
+    n, c, h, wd = x.shape
+    cout = w.shape[0]
+    if tuple(w.shape) != (cout, c, 3, 3) or not w.is_contiguous(memory_format=cl) or \
+            not x.is_contiguous(memory_format=cl) or w.dtype != x.dtype or (b is not None and b.dtype != x.dtype):
+        raise RuntimeError("conv3x3: channels-last input and [cout, cin, 3, 3] weight, bias of one dtype expected")
+    y = torch.empty((n, (h - 1) // stride + 1, (wd - 1) // stride + 1, cout), dtype=x.dtype,
+                    device=x.device).permute(0, 3, 1, 2)
+    if residual is not None and (residual.shape != y.shape or residual.dtype != y.dtype or
+                                 not residual.is_contiguous(memory_format=cl)):
+        raise RuntimeError("conv3x3: channels-last residual of the output's shape and dtype expected")
+    _lib.call("tm_conv3x3", _dtype_code(x), _p(x), _p(w), _p(b), _p(residual), _p(y), n, h, wd, c, cout,
+              int(stride), int(relu), _stream())
     return y
 
 
@@ -369,23 +397,17 @@ def train_pieces(n_tiles, chunk, h=224, w=224, elem_bytes=4, max_pieces=64):
     return size
 
 
-class RetCCLResNet50(nn.Module):
-    """``ResNet(Bottleneck, [3, 4, 6, 3])`` with ``fc = Identity``: tiles [n, 3, 224, 224] ->
-    features [n, 2048] fp32."""
+class _FrozenTileEncoder(nn.Module):
+    """What the frozen tile encoders share: the compute-dtype / chunk controls, the ``_fold_key``
+    refolding contract, the weight cast of the train path, the stem and the chunked forward
+    scaffolding (``_encode``: tiles [n, 3, H, W] -> body features [n, ``width``] fp32).  A subclass
+    builds the modules, sets ``width`` / ``_name`` and supplies ``_fold_all``, ``_forward_folded``,
+    ``_forward_train_fused`` and ``_forward_modules``; the body is every tensor outside ``fc``."""
 
-    def __init__(self, momentum_bn=0.1, chunk=512):
-        super().__init__()
-        self.inplanes = 64
-        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
-        self.bn1 = nn.BatchNorm2d(64, momentum=momentum_bn)
-        self.relu = nn.ReLU(inplace=True)
-        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
-        self.layer1 = self._stage(64, 3, 1, momentum_bn)
-        self.layer2 = self._stage(128, 4, 2, momentum_bn)
-        self.layer3 = self._stage(256, 6, 2, momentum_bn)
-        self.layer4 = self._stage(512, 3, 2, momentum_bn)
-        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
-        self.fc = nn.Identity()                         # model_interface.py:245
+    width = 0
+    _name = "encoder"
+
+    def _init_controls(self, chunk):
         self.compute_dtype = torch.bfloat16
         self.chunk = chunk
         self.channels_last = True
@@ -393,18 +415,9 @@ class RetCCLResNet50(nn.Module):
         self._folded_key = None
         self._cast = None               # train mode: conv weights in the compute dtype, channels-last
         self._cast_key = None
-        for p in self.parameters():                     # model_interface.py:243-244
-            p.requires_grad = False
 
-    def _stage(self, planes, blocks, stride, momentum_bn):
-        down = None
-        if stride != 1 or self.inplanes != planes * 4:
-            down = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False),
-                                 nn.BatchNorm2d(planes * 4, momentum=momentum_bn))
-        layers = [Bottleneck(self.inplanes, planes, stride, down, momentum_bn)]
-        self.inplanes = planes * 4
-        layers += [Bottleneck(self.inplanes, planes, momentum_bn=momentum_bn) for _ in range(1, blocks)]
-        return nn.Sequential(*layers)
+    def _body_parameters(self):
+        return [p for n, p in self.named_parameters() if not n.startswith("fc.")]
 
     def set_compute_dtype(self, dtype):
         if dtype not in (torch.bfloat16, torch.float32):
@@ -421,134 +434,60 @@ class RetCCLResNet50(nn.Module):
         self._folded = None
         return super().train(mode)
 
-    def load_retccl_checkpoint(self, path):
-        """``load_state_dict(torch.load(path), strict=False)`` as the reference does (:242), with
-        the safe loader; the 128-way ``fc`` of the checkpoint is dropped (fc is Identity)."""
-        sd = torch.load(path, map_location="cpu", weights_only=True)
-        return self.load_state_dict({k: v for k, v in sd.items() if not k.startswith("fc.")}, strict=False)
-
-    # ------------------------------------------------------------------ eval: folded convolutions
     def _fold_key(self):
-        """Identity of every parameter and buffer the folded weights derive from (storage and
+        """Identity of every body parameter and buffer the folded weights derive from (storage and
         in-place version counter): a checkpoint loaded through a parent module, ``.to()``, an
         in-place weight edit or a BatchNorm statistics update all change it, so the next eval
         forward re-folds instead of reading stale conv+BN weights."""
         return tuple((t.data_ptr(), t._version, t.dtype) for t in
-                     list(self.parameters()) + list(self.buffers()))
+                     self._body_parameters() + [b for n, b in self.named_buffers() if not n.startswith("fc.")])
 
-    def _fold_all(self):
-        dt, cl = self.compute_dtype, self.channels_last
-        f = {"stem": _fold(self.conv1, self.bn1, dt, cl), "blocks": []}
-        if dt == torch.bfloat16:
-            f["stem_packed"] = _pack_stem(f["stem"][0])
-        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
-            for blk in stage:
-                d = None
-                if blk.downsample is not None:
-                    d = _fold(blk.downsample[0], blk.downsample[1], dt, cl) + (blk.downsample[0].stride,)
-                f["blocks"].append((_fold(blk.conv1, blk.bn1, dt, cl), _fold(blk.conv2, blk.bn2, dt, cl) + (blk.stride,),
-                                    _fold(blk.conv3, blk.bn3, dt, cl), d))
-        self._folded = f
-
-    def _forward_folded(self, x):
-        """Eval mode, BN folded.  On the GPU with channels-last activations: every 1x1 convolution
-        one hipBLASLt GEMM with its epilogue (conv1: bias + ReLU; downsample: bias; conv3: bias +
-        residual + ReLU -- the block output is written once), the 3x3 / stem convolutions through
-        MIOpen without bias, then bias + ReLU in one in-place pass."""
-        f = self._folded
-        w, b = f["stem"]
-        if self.channels_last and x.is_cuda:
-            if "stem_packed" in f and x.dtype == torch.bfloat16 and _stem_fused_enabled():
-                x = _stem_conv_pool(x, f["stem_packed"], b)
-            else:
-                y = _lib_conv2d(_cl(x), w, None, stride=2, padding=3)
-                x = _stem_pool_(y, b) if y.dtype == torch.bfloat16 else _lib_max_pool(_bias_act_(y, b))
-            for (w1, b1), (w2, b2, s2), (w3, b3), d in f["blocks"]:
-                y = _conv1x1_gemm(x, w1, b1, True)
-                y = _bias_act_(_lib_conv2d(y, w2, None, stride=s2, padding=1), b2)
-                if d is None:
-                    idt = x
-                else:
-                    idt = _conv1x1_gemm(_subsample(x, d[2][0]), d[0], d[1], False)
-                x = _conv1x1_gemm(y, w3, b3, True, residual=idt)
-            return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
-        x = _lib_max_pool(F.relu(_lib_conv2d(x, w, b, stride=2, padding=3)))
-        for (w1, b1), (w2, b2, s2), (w3, b3), d in f["blocks"]:
-            y = F.relu(_lib_conv2d(x, w1, b1))
-            y = F.relu(_lib_conv2d(y, w2, b2, stride=s2, padding=1))
-            y = _lib_conv2d(y, w3, b3)
-            idt = x if d is None else _lib_conv2d(x, d[0], d[1], stride=d[2][0])
-            x = F.relu(y + idt)
-        return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
-
-    def _forward_train_fused(self, x):
-        """Train mode (batch-statistics BatchNorm, frozen parameters, no autograd) on the GPU.
-        The bag is held as pieces of ``train_pieces(N, chunk)`` tiles (every convolution / pooling
-        on one piece, < 2^31 elements) while each BatchNorm's statistics span all pieces
-        (tm_bn_train_stats).  Convolutions without bias (1x1: hipBLASLt GEMM; 3x3 / stem: MIOpen),
-        each BatchNorm one statistics pass + one apply pass fused with its ReLU, and bn3 + (BN'd
-        downsample) identity + ReLU one pass (tm_bn_apply)."""
+    def _cast_weights(self):
+        """Train mode: the convolution weights in the compute dtype, channels-last (refreshed when
+        ``_fold_key`` changes)."""
         key = self._fold_key()
         if self._cast is None or self._cast_key != key:
             self._cast = {n: _cl(p.detach().to(self.compute_dtype)) for n, p in self.named_parameters()
                           if p.dim() == 4}
             self._cast_key = key
-        w = self._cast
-        ws = torch.empty(self._bn_ws_floats(), dtype=torch.float32, device=x.device)
-        piece = train_pieces(x.shape[0], self.chunk, x.shape[2], x.shape[3], x.element_size())
+        return self._cast
+
+    def _stem_folded(self, x):
+        """The eval stem on the GPU, BN folded: one hand-written pass for bf16 tiles, else the
+        library convolution + bias / ReLU / max-pool."""
+        f = self._folded
+        w, b = f["stem"]
+        if "stem_packed" in f and x.dtype == torch.bfloat16 and _stem_fused_enabled():
+            return _stem_conv_pool(x, f["stem_packed"], b)
+        y = _lib_conv2d(_cl(x), w, None, stride=2, padding=3)
+        return _stem_pool_(y, b) if y.dtype == torch.bfloat16 else _lib_max_pool(_bias_act_(y, b))
+
+    def _stem_train(self, x, w, ws, piece):
+        """The train-mode stem (batch statistics over the whole bag) as a list of bag pieces."""
         if x.dtype == torch.bfloat16 and _stem_fused_enabled():
             # the stem in two hand-written passes over the tiles (statistics, then conv + BN + ReLU +
             # pool): the 112 x 112 x 64 conv output is never stored
             if "stem_packed" not in w:
                 w["stem_packed"] = _pack_stem(w["conv1.weight"])
             st = _stem_bn_stats(x, w["stem_packed"], self.bn1)
-            xs = [_stem_conv_pool_bn(x[i:i + piece], w["stem_packed"], st) for i in range(0, x.shape[0], piece)]
-        else:
-            xs = [_cl(_lib_conv2d(_cl(x[i:i + piece]), w["conv1.weight"], None, stride=2, padding=3))
-                  for i in range(0, x.shape[0], piece)]
-            st = _bn_train_stats(xs, self.bn1, ws)
-            if x.dtype == torch.bfloat16:
-                xs = [_stem_pool_bn_(p, st) for p in xs]
-            else:
-                xs = [_lib_max_pool(_bn_apply_(p, st)) for p in xs]
-        for si, stage in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), start=1):
-            for bi, blk in enumerate(stage):
-                pre = f"layer{si}.{bi}."
-                ys = [_conv1x1_gemm(p, w[pre + "conv1.weight"], None, False) for p in xs]
-                st = _bn_train_stats(ys, blk.bn1, ws)
-                ys = [_cl(_lib_conv2d(_bn_apply_(y, st), w[pre + "conv2.weight"], None, stride=blk.stride, padding=1))
-                      for y in ys]
-                st = _bn_train_stats(ys, blk.bn2, ws)
-                ys = [_conv1x1_gemm(_bn_apply_(y, st), w[pre + "conv3.weight"], None, False) for y in ys]
-                st3 = _bn_train_stats(ys, blk.bn3, ws)
-                if blk.downsample is None:
-                    for y, p in zip(ys, xs):
-                        _bn_apply_(y, st3, residual=p)
-                else:
-                    s = blk.downsample[0].stride[0]
-                    ds = [_conv1x1_gemm(_subsample(p, s), w[pre + "downsample.0.weight"], None, False) for p in xs]
-                    sd = _bn_train_stats(ds, blk.downsample[1], ws)
-                    for y, d in zip(ys, ds):
-                        _bn_apply_(y, st3, residual=d, rst=sd)
-                    del ds
-                xs = ys
-        return torch.cat([torch.flatten(F.adaptive_avg_pool2d(p, 1), 1) for p in xs])
+            return [_stem_conv_pool_bn(x[i:i + piece], w["stem_packed"], st) for i in range(0, x.shape[0], piece)]
+        xs = [_cl(_lib_conv2d(_cl(x[i:i + piece]), w["conv1.weight"], None, stride=2, padding=3))
+              for i in range(0, x.shape[0], piece)]
+        st = _bn_train_stats(xs, self.bn1, ws)
+        if x.dtype == torch.bfloat16:
+            return [_stem_pool_bn_(p, st) for p in xs]
+        return [_lib_max_pool(_bn_apply_(p, st)) for p in xs]
 
     @staticmethod
     def _bn_ws_floats():
         from . import _lib
         return _lib.query("tm_bn_train_workspace", 2048)
 
-    def _forward_modules(self, x):
-        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
-        return self.fc(torch.flatten(self.avgpool(x), 1))
-
-    def forward(self, x):
+    def _encode(self, x):
         if not x.is_cuda:
-            raise RuntimeError("RetCCL encoder (MI355X path) needs a GPU tensor")
+            raise RuntimeError(f"{self._name} (MI355X path) needs a GPU tensor")
         dt = self.compute_dtype
-        out = torch.empty(x.shape[0], 2048, dtype=torch.float32, device=x.device)
+        out = torch.empty(x.shape[0], self.width, dtype=torch.float32, device=x.device)
         if not self.training:
             key = self._fold_key()
             if self._folded is None or self._folded_key != key:
@@ -557,7 +496,7 @@ class RetCCLResNet50(nn.Module):
         if self.training and self.channels_last and \
                 not self.conv1.weight.is_contiguous(memory_format=torch.channels_last):
             self.to(memory_format=torch.channels_last)
-        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self._body_parameters())
         # train-mode BatchNorm normalises with the statistics of the whole [B*bag] batch the
         # reference feeds model_ft in one call (model_interface.py:303-309): the fused train path
         # holds the bag in pieces whose statistics are combined; eval chunks are per-tile exact.
@@ -592,16 +531,294 @@ class RetCCLResNet50(nn.Module):
         return out
 
 
+class RetCCLResNet50(_FrozenTileEncoder):
+    """``ResNet(Bottleneck, [3, 4, 6, 3])`` with ``fc = Identity``: tiles [n, 3, 224, 224] ->
+    features [n, 2048] fp32."""
+
+    width = 2048
+    _name = "RetCCL encoder"
+
+    def __init__(self, momentum_bn=0.1, chunk=512):
+        super().__init__()
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64, momentum=momentum_bn)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._stage(64, 3, 1, momentum_bn)
+        self.layer2 = self._stage(128, 4, 2, momentum_bn)
+        self.layer3 = self._stage(256, 6, 2, momentum_bn)
+        self.layer4 = self._stage(512, 3, 2, momentum_bn)
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self.fc = nn.Identity()                         # model_interface.py:245
+        self._init_controls(chunk)
+        for p in self.parameters():                     # model_interface.py:243-244
+            p.requires_grad = False
+
+    def _stage(self, planes, blocks, stride, momentum_bn):
+        down = None
+        if stride != 1 or self.inplanes != planes * 4:
+            down = nn.Sequential(nn.Conv2d(self.inplanes, planes * 4, 1, stride=stride, bias=False),
+                                 nn.BatchNorm2d(planes * 4, momentum=momentum_bn))
+        layers = [Bottleneck(self.inplanes, planes, stride, down, momentum_bn)]
+        self.inplanes = planes * 4
+        layers += [Bottleneck(self.inplanes, planes, momentum_bn=momentum_bn) for _ in range(1, blocks)]
+        return nn.Sequential(*layers)
+
+    def load_retccl_checkpoint(self, path):
+        """``load_state_dict(torch.load(path), strict=False)`` as the reference does (:242), with
+        the safe loader; the 128-way ``fc`` of the checkpoint is dropped (fc is Identity)."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        return self.load_state_dict({k: v for k, v in sd.items() if not k.startswith("fc.")}, strict=False)
+
+    # ------------------------------------------------------------------ eval: folded convolutions
+    def _fold_all(self):
+        dt, cl = self.compute_dtype, self.channels_last
+        f = {"stem": _fold(self.conv1, self.bn1, dt, cl), "blocks": []}
+        if dt == torch.bfloat16:
+            f["stem_packed"] = _pack_stem(f["stem"][0])
+        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
+            for blk in stage:
+                d = None
+                if blk.downsample is not None:
+                    d = _fold(blk.downsample[0], blk.downsample[1], dt, cl) + (blk.downsample[0].stride,)
+                f["blocks"].append((_fold(blk.conv1, blk.bn1, dt, cl), _fold(blk.conv2, blk.bn2, dt, cl) + (blk.stride,),
+                                    _fold(blk.conv3, blk.bn3, dt, cl), d))
+        self._folded = f
+
+    def _forward_folded(self, x):
+        """Eval mode, BN folded.  On the GPU with channels-last activations: every 1x1 convolution
+        one hipBLASLt GEMM with its epilogue (conv1: bias + ReLU; downsample: bias; conv3: bias +
+        residual + ReLU -- the block output is written once), the 3x3 / stem convolutions through
+        MIOpen without bias, then bias + ReLU in one in-place pass."""
+        f = self._folded
+        w, b = f["stem"]
+        if self.channels_last and x.is_cuda:
+            x = self._stem_folded(x)
+            for (w1, b1), (w2, b2, s2), (w3, b3), d in f["blocks"]:
+                y = _conv1x1_gemm(x, w1, b1, True)
+                y = _bias_act_(_lib_conv2d(y, w2, None, stride=s2, padding=1), b2)
+                if d is None:
+                    idt = x
+                else:
+                    idt = _conv1x1_gemm(_subsample(x, d[2][0]), d[0], d[1], False)
+                x = _conv1x1_gemm(y, w3, b3, True, residual=idt)
+            return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
+        x = _lib_max_pool(F.relu(_lib_conv2d(x, w, b, stride=2, padding=3)))
+        for (w1, b1), (w2, b2, s2), (w3, b3), d in f["blocks"]:
+            y = F.relu(_lib_conv2d(x, w1, b1))
+            y = F.relu(_lib_conv2d(y, w2, b2, stride=s2, padding=1))
+            y = _lib_conv2d(y, w3, b3)
+            idt = x if d is None else _lib_conv2d(x, d[0], d[1], stride=d[2][0])
+            x = F.relu(y + idt)
+        return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
+
+    def _forward_train_fused(self, x):
+        """Train mode (batch-statistics BatchNorm, frozen parameters, no autograd) on the GPU.
+        The bag is held as pieces of ``train_pieces(N, chunk)`` tiles (every convolution / pooling
+        on one piece, < 2^31 elements) while each BatchNorm's statistics span all pieces
+        (tm_bn_train_stats).  Convolutions without bias (1x1: hipBLASLt GEMM; 3x3 / stem: MIOpen),
+        each BatchNorm one statistics pass + one apply pass fused with its ReLU, and bn3 + (BN'd
+        downsample) identity + ReLU one pass (tm_bn_apply)."""
+        w = self._cast_weights()
+        ws = torch.empty(self._bn_ws_floats(), dtype=torch.float32, device=x.device)
+        piece = train_pieces(x.shape[0], self.chunk, x.shape[2], x.shape[3], x.element_size())
+        xs = self._stem_train(x, w, ws, piece)
+        for si, stage in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), start=1):
+            for bi, blk in enumerate(stage):
+                pre = f"layer{si}.{bi}."
+                ys = [_conv1x1_gemm(p, w[pre + "conv1.weight"], None, False) for p in xs]
+                st = _bn_train_stats(ys, blk.bn1, ws)
+                ys = [_cl(_lib_conv2d(_bn_apply_(y, st), w[pre + "conv2.weight"], None, stride=blk.stride, padding=1))
+                      for y in ys]
+                st = _bn_train_stats(ys, blk.bn2, ws)
+                ys = [_conv1x1_gemm(_bn_apply_(y, st), w[pre + "conv3.weight"], None, False) for y in ys]
+                st3 = _bn_train_stats(ys, blk.bn3, ws)
+                if blk.downsample is None:
+                    for y, p in zip(ys, xs):
+                        _bn_apply_(y, st3, residual=p)
+                else:
+                    s = blk.downsample[0].stride[0]
+                    ds = [_conv1x1_gemm(_subsample(p, s), w[pre + "downsample.0.weight"], None, False) for p in xs]
+                    sd = _bn_train_stats(ds, blk.downsample[1], ws)
+                    for y, d in zip(ys, ds):
+                        _bn_apply_(y, st3, residual=d, rst=sd)
+                    del ds
+                xs = ys
+        return torch.cat([torch.flatten(F.adaptive_avg_pool2d(p, 1), 1) for p in xs])
+
+    def _forward_modules(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return self.fc(torch.flatten(self.avgpool(x), 1))
+
+    def forward(self, x):
+        return self._encode(x)
+
+
 def retccl_resnet50(**kw):
     """``ResNet.resnet50(num_classes=128, mlp=False, two_branch=False, normlinear=True)`` with
     ``fc = Identity`` and frozen parameters (model_interface.py:238-245)."""
     return RetCCLResNet50(**kw)
 
 
+class BasicBlock(nn.Module):
+    """3x3 (stride) -> 3x3 with BN after each, residual + ReLU (torchvision's BasicBlock)."""
+
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn2(self.conv2(out))
+        idt = self.downsample(x) if self.downsample is not None else x
+        return self.relu(out + idt)
+
+
+class ResNet18(_FrozenTileEncoder):
+    """``Model.backbone: resnet18`` (model_interface.py:226-234): torchvision's ``resnet18`` layout
+    (same module / parameter / buffer names, so an ImageNet checkpoint loads), every body parameter
+    frozen, ``fc`` replaced by a trainable ``nn.Linear(512, 512)``: tiles [n, 3, H, W] -> [n, 512]
+    fp32.  The 16 3x3 convolutions (92 % of the FLOPs) run on the hand-written implicit-GEMM
+    kernel (csrc/conv3x3.hip) in both modes: eval with BN folded and bias / residual / ReLU in its
+    epilogue (a BasicBlock is two launches, + subsample and a 1x1 GEMM where it downsamples); train
+    mode without bias, each BatchNorm one whole-bag statistics pass + one apply pass fused with the
+    ReLU (bn2 with the -- BN'd -- identity).  The kernel addresses with 64 bits, so only the stem
+    (fp32) and the 1x1 downsample GEMMs keep the library piece limits."""
+
+    width = 512
+    _name = "ResNet-18 encoder"
+
+    def __init__(self, chunk=512):
+        super().__init__()
+        self.inplanes = 64
+        self.conv1 = nn.Conv2d(3, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._stage(64, 1)
+        self.layer2 = self._stage(128, 2)
+        self.layer3 = self._stage(256, 2)
+        self.layer4 = self._stage(512, 2)
+        self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
+        self._init_controls(chunk)
+        for p in self.parameters():                     # model_interface.py:232-233
+            p.requires_grad = False
+        self.fc = nn.Linear(512, 512)                   # :234: created after the freeze, trainable
+
+    def _stage(self, planes, stride):
+        down = None
+        if stride != 1 or self.inplanes != planes:
+            down = nn.Sequential(nn.Conv2d(self.inplanes, planes, 1, stride=stride, bias=False),
+                                 nn.BatchNorm2d(planes))
+        layers = [BasicBlock(self.inplanes, planes, stride, down), BasicBlock(planes, planes)]
+        self.inplanes = planes
+        return nn.Sequential(*layers)
+
+    def load_imagenet_checkpoint(self, path):
+        """``load_state_dict(torch.load(path), strict=False)`` with the safe loader; the 1000-way
+        ``fc`` of an ImageNet checkpoint is dropped (fc is the new 512 -> 512 layer)."""
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        return self.load_state_dict({k: v for k, v in sd.items() if not k.startswith("fc.")}, strict=False)
+
+    def _blocks(self):
+        for si, stage in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), start=1):
+            for bi, blk in enumerate(stage):
+                yield f"layer{si}.{bi}.", blk
+
+    def _fold_all(self):
+        dt, cl = self.compute_dtype, self.channels_last
+        f = {"stem": _fold(self.conv1, self.bn1, dt, cl), "blocks": []}
+        if dt == torch.bfloat16:
+            f["stem_packed"] = _pack_stem(f["stem"][0])
+        for _, blk in self._blocks():
+            d = None
+            if blk.downsample is not None:
+                d = _fold(blk.downsample[0], blk.downsample[1], dt, cl) + (blk.downsample[0].stride[0],)
+            f["blocks"].append((_fold(blk.conv1, blk.bn1, dt, cl) + (blk.stride,), _fold(blk.conv2, blk.bn2, dt, cl), d))
+        self._folded = f
+
+    def _forward_folded(self, x):
+        """Eval mode, BN folded.  On the GPU with channels-last activations a BasicBlock is
+        y = conv3x3(x, w1) + b1 -> ReLU, out = conv3x3(y, w2) + b2 + identity -> ReLU, each one
+        tm_conv3x3 launch that writes its output once; identity = x or the 1x1 GEMM of the
+        subsampled x."""
+        f = self._folded
+        if self.channels_last and x.is_cuda:
+            x = self._stem_folded(x)
+            for (w1, b1, s1), (w2, b2), d in f["blocks"]:
+                y = _conv3x3(x, w1, b1, s1, True)
+                idt = x if d is None else _conv1x1_gemm(_subsample(x, d[2]), d[0], d[1], False)
+                x = _conv3x3(y, w2, b2, 1, True, residual=idt)
+            return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
+        w, b = f["stem"]
+        x = _lib_max_pool(F.relu(_lib_conv2d(x, w, b, stride=2, padding=3)))
+        for (w1, b1, s1), (w2, b2), d in f["blocks"]:
+            y = F.relu(_lib_conv2d(x, w1, b1, stride=s1, padding=1))
+            y = _lib_conv2d(y, w2, b2, padding=1)
+            idt = x if d is None else _lib_conv2d(x, d[0], d[1], stride=d[2])
+            x = F.relu(y + idt)
+        return torch.flatten(F.adaptive_avg_pool2d(x, 1), 1)
+
+    def _forward_train_fused(self, x):
+        """Train mode (batch-statistics BatchNorm, frozen parameters, no autograd) on the GPU: the
+        bag as pieces of ``train_pieces(N, chunk)`` tiles, each BatchNorm's statistics over all of
+        them (tm_bn_train_stats); 3x3 convolutions without bias on tm_conv3x3, bn1 + ReLU one
+        in-place pass, bn2 + (BN'd downsample) identity + ReLU one pass (tm_bn_apply)."""
+        w = self._cast_weights()
+        ws = torch.empty(self._bn_ws_floats(), dtype=torch.float32, device=x.device)
+        piece = train_pieces(x.shape[0], self.chunk, x.shape[2], x.shape[3], x.element_size())
+        xs = self._stem_train(x, w, ws, piece)
+        for pre, blk in self._blocks():
+            ys = [_conv3x3(p, w[pre + "conv1.weight"], None, blk.stride, False) for p in xs]
+            st = _bn_train_stats(ys, blk.bn1, ws)
+            ys = [_conv3x3(_bn_apply_(y, st), w[pre + "conv2.weight"], None, 1, False) for y in ys]
+            st2 = _bn_train_stats(ys, blk.bn2, ws)
+            if blk.downsample is None:
+                for y, p in zip(ys, xs):
+                    _bn_apply_(y, st2, residual=p)
+            else:
+                s = blk.downsample[0].stride[0]
+                ds = [_conv1x1_gemm(_subsample(p, s), w[pre + "downsample.0.weight"], None, False) for p in xs]
+                sd = _bn_train_stats(ds, blk.downsample[1], ws)
+                for y, d in zip(ys, ds):
+                    _bn_apply_(y, st2, residual=d, rst=sd)
+                del ds
+            xs = ys
+        return torch.cat([torch.flatten(F.adaptive_avg_pool2d(p, 1), 1) for p in xs])
+
+    def _forward_modules(self, x):
+        x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
+        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+        return torch.flatten(self.avgpool(x), 1)
+
+    def forward(self, x):
+        """[n, 3, H, W] -> fc(average-pooled body features) [n, 512] fp32; the gradient reaches
+        ``fc`` (HIP GEMM, ops.linear) and stops at the frozen body."""
+        from . import ops
+        return ops.linear(self.fc, self._encode(x))
+
+
+def resnet18(**kw):
+    """torchvision ``resnet18`` as ``backbone: resnet18`` uses it (model_interface.py:226-234):
+    frozen body, trainable ``fc = nn.Linear(512, 512)``."""
+    return ResNet18(**kw)
+
+
 class ImageBagModel(nn.Module):
     """``ModelInterface.forward``'s image path (model_interface.py:300-316): tiles
-    ``[B, bag, 3, H, W]`` -> frozen encoder -> ``[B, bag, 2048]`` on the device -> the MIL model
-    (TransMIL(n_classes, 2048) runs its RCC-2048 _fc1 branch on the fused engine)."""
+    ``[B, bag, 3, H, W]`` -> frozen encoder -> ``[B, bag, the encoder's width]`` on the device ->
+    the MIL model (TransMIL(n_classes, 2048) runs its RCC-2048 _fc1 branch on the fused engine,
+    TransMIL(n_classes, 512) behind ``resnet18`` its 512 -> 512 branch)."""
 
     def __init__(self, model_ft: nn.Module, model: nn.Module):
         super().__init__()

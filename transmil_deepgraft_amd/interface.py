@@ -920,7 +920,12 @@ class TransMILTask(nn.Module):
         return loss
 
     def configure_optimizers(self):
-        opt = create_optimizer(self.model, self.opt, self.lr, self.weight_decay)
+        # the reference builds its optimizer from self.model, never from model_ft
+        # (model_interface.py:862-877): an image model's encoder -- resnet18's trainable fc included --
+        # is not optimised
+        from .encoder import ImageBagModel
+        mil = self.model.model if isinstance(self.model, ImageBagModel) else self.model
+        opt = create_optimizer(mil, self.opt, self.lr, self.weight_decay)
         sched = {"scheduler": torch.optim.lr_scheduler.ReduceLROnPlateau(
             opt.base_optimizer if isinstance(opt, Lookahead) else opt, mode="min", factor=0.5),
             "monitor": "val_loss", "frequency": 10}
@@ -950,9 +955,11 @@ class TransMILTask(nn.Module):
         ``forward_ce`` does) and the B slide / patient names as lists."""
         bags, label, meta = batch
         names, patients = meta[0], meta[-1]
-        if bags.dim() == 2:
+        from .encoder import ImageBagModel
+        nd = 5 if isinstance(self.model, ImageBagModel) else 3      # tile bags [B, N, 3, H, W]
+        if bags.dim() == nd - 1:
             bags = bags.unsqueeze(0)
-        elif bags.dim() > 3:
+        elif bags.dim() > nd:
             bags = bags.squeeze(0)
         B = bags.shape[0]
         if not torch.is_tensor(label):
