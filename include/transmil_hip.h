@@ -489,6 +489,31 @@ int tm_conv1x1_tune(int dtype, const void* x, const void* w, const void* bias, c
  * alias x.  Bitwise reproducible (no atomics).  Every refusal's message begins "conv3x3:". */
 int tm_conv3x3(int dtype, const void* x, const void* w, const void* bias, const void* residual, void* y,
                long long n, int h, int wd, int cin, int cout, int stride, int relu, void* stream);
+/* One convolution stage of the `simple` tile backbone (code/models/model_interface.py:270-281:
+ * Conv2d(3, 20, 5) / Conv2d(20, 50, 5), each + ReLU + MaxPool2d(2, 2)) in one pass (conv5x5.hip):
+ *   out[n, pr, pc, c] = maxpool2x2/2(relu(conv5x5_valid(x, w) + bias))[n, c, pr, pc],
+ * stride 1, no padding, floor-mode pool: ph = (h - 4) / 2, pw = (w - 4) / 2 (an odd convolution output
+ * drops its last row / column); the convolution output never reaches HBM.  Implicit GEMM on the MFMA
+ * units in both modes: dtype TM_BF16 (bf16 x, wp, out; fp32 accumulation, one rounding after the
+ * pool) or TM_F32.  (cin, cout) = (3, 20) or (20, 50) only; h, w in 6..32768; n >= 1, x and out
+ * addressed with 64-bit offsets (no 2^31 limit).
+ *   x     (3, 20):  [n, 3, h, w] at element strides (sn, sc, sh, sw): NCHW or channels-last.
+ *         (20, 50): the first stage's output layout: channels-last pixels of 24 channels, 20 .. 23
+ *                   zero (sc = 1, sw = 24, sh and sn multiples of 8, 16-byte aligned).
+ *   wp    the weights packed on the host in MFMA fragment order, dtype elements
+ *         [NS][NU][2][32][8]: element j of fragment f = 2 s + hf of output channel 32 u + r at
+ *         [s][u][hf][r][j], zero where no weight is named.
+ *         (3, 20):  NS = 8, NU = 1; f = 3 ky + sub, j = 4 (kx - 2 sub) + c  (kx = 5, c = 3: zero).
+ *         (20, 50): NS = 38, NU = 2; f = 3 (5 ky + kx) + sub, j = c - 8 sub  (c >= 20: zero).
+ *   bias  fp32 [cout].
+ *   out   tile n at out + n * so; pixel (pr, pc) holds cpo channels (cpo even, cout <= cpo <= 32 NU;
+ *         channels cout .. cpo - 1 are written as zeros), and the `tail` elements after a tile's
+ *         ph * pw * cpo are written as zeros (so even, so >= ph * pw * cpo + tail).  The second stage
+ *         with cpo = 50, so = 140480, tail = 30 writes the rows of the Linear's K-padded A matrix.
+ * Bitwise reproducible (no atomics).  Every refusal's message begins "conv5x5:". */
+int tm_conv5x5_relu_pool(int dtype, const void* x, const void* wp, const float* bias, void* out, long long n, int h,
+                         int w, int cin, int cout, long long sn, long long sc, long long sh, long long sw,
+                         long long so, int cpo, int tail, void* stream);
 /* Train-mode BatchNorm2d over a channels-last activation given as npieces (1..64) row pieces
  * xs[p] of [rows[p], C] (host arrays; C a power of two, 8..2048; nn.BatchNorm2d.forward in
  * training, code/models/ResNet.py:95-117 under model.train()): batch statistics over all pieces

@@ -18,6 +18,11 @@ TransMIL(2, 512).  ``--compare-library R`` then also times the same encoder with
 convolutions routed through the library (MIOpen convolution + tm_bias_act, residual add + ReLU as
 torch passes), R rounds alternating with the hand-written kernel; the route exists in this script
 only.
+
+``--backbone simple`` runs the MIL-AB tile CNN of the ``AttMIL_simple_*`` configs (two fused 5x5
+convolution + ReLU + max-pool launches on tm_conv5x5_relu_pool, Linear(140450, 1024) + ReLU on
+tm_gemm) -> AttMIL(2, 1024).  ``--compare-library R`` times the library route beside it: MIOpen
+convolutions, torch ReLU / max-pool, the same GEMM over the NCHW-flattened rows.
 """
 from __future__ import annotations
 
@@ -35,6 +40,7 @@ sys.path.insert(0, ROOT)
 BF16_PEAK_TFS = 2500.0
 R50_GFLOP_PER_TILE = 4.09   # ResNet-50 forward at 224x224, multiply-adds x 2 (conv + fc-free)
 R18_GFLOP_PER_TILE = 3.63   # ResNet-18 forward at 224x224, multiply-adds x 2 (3.35 of them 3x3 convolutions)
+SIMPLE_GFLOP_PER_TILE = 0.995   # 0.145 (3 -> 20 at 220 x 220) + 0.562 (20 -> 50 at 106 x 106) + 0.288 (Linear 140450 -> 1024)
 
 
 def library_conv3x3(x, w, b, stride, relu, residual=None):
@@ -52,6 +58,39 @@ def library_conv3x3(x, w, b, stride, relu, residual=None):
     elif relu:
         y.relu_()
     return y
+
+
+class LibrarySimple:
+    """encoder.SimpleCNN's forward on the library route: MIOpen convolutions (channels-last bf16), torch
+    ReLU / max-pool, then the same split-K tm_gemm + tm_bias_act over the NCHW-flattened, K-padded rows
+    (the weight zero-padded in the reference's own column order)."""
+
+    def __init__(self, enc):
+        from transmil_deepgraft_amd.encoder import SIMPLE_K, SIMPLE_KP
+        m, dt = dict(enc.named_children()), enc.compute_dtype
+        self.enc, self.k, self.kp = enc, SIMPLE_K, SIMPLE_KP
+        cl = torch.channels_last
+        self.w1, self.b1 = m["0"].weight.detach().to(dt).contiguous(memory_format=cl), m["0"].bias.detach().to(dt)
+        self.w2, self.b2 = m["3"].weight.detach().to(dt).contiguous(memory_format=cl), m["3"].bias.detach().to(dt)
+        self.wfc = torch.zeros(enc.width, SIMPLE_KP, dtype=dt, device=m["7"].weight.device)
+        self.wfc[:, :SIMPLE_K] = m["7"].weight.detach()
+        self.bfc = m["7"].bias.detach().float().contiguous()
+
+    def __call__(self, x):
+        import torch.nn.functional as F
+        from transmil_deepgraft_amd.encoder import simple_fc
+        enc = self.enc
+        out = torch.empty(x.shape[0], enc.width, dtype=torch.float32, device=x.device)
+        with torch.no_grad():
+            for s in range(0, x.shape[0], enc.chunk):
+                xc = x[s:s + enc.chunk].to(enc.compute_dtype).contiguous(memory_format=torch.channels_last)
+                y = F.max_pool2d(F.relu_(F.conv2d(xc, self.w1, self.b1)), 2, 2)
+                y = F.max_pool2d(F.relu_(F.conv2d(y, self.w2, self.b2)), 2, 2)
+                a = torch.empty(y.shape[0], self.kp, dtype=y.dtype, device=y.device)
+                a[:, :self.k].view(y.shape[0], 50, 53, 53).copy_(y)
+                a[:, self.k:].zero_()
+                simple_fc(a, self.wfc, self.bfc, out[s:s + y.shape[0]])
+        return out
 
 
 def timed(fn, steps):
@@ -81,23 +120,26 @@ def main():
     # (profiles/r04p_c5_find.jsonl); --no-benchmark keeps MIOpen's immediate-mode heuristics
     ap.add_argument("--benchmark", action=argparse.BooleanOptionalAction, default=True,
                     help="torch.backends.cudnn.benchmark (MIOpen find)")
-    ap.add_argument("--backbone", default="retccl", choices=["retccl", "resnet18"])
+    ap.add_argument("--backbone", default="retccl", choices=["retccl", "resnet18", "simple"])
     ap.add_argument("--compare-library", type=int, default=0, metavar="ROUNDS",
-                    help="resnet18: also time the encoder with library 3x3 convolutions, alternating ROUNDS times")
+                    help="resnet18 / simple: also time the encoder with library convolutions, alternating ROUNDS times")
     a = ap.parse_args()
     torch.backends.cudnn.benchmark = a.benchmark
     from transmil_deepgraft_amd import encoder as encoder_module
-    from transmil_deepgraft_amd.encoder import ImageBagModel, resnet18, retccl_resnet50
+    from transmil_deepgraft_amd.encoder import ImageBagModel, resnet18, retccl_resnet50, simple_cnn
     from transmil_deepgraft_amd.interface import GradAllReduce, TransMILTask
-    from transmil_deepgraft_amd.models import TransMIL
+    from transmil_deepgraft_amd.models import AttMIL, TransMIL
     dev = torch.device("cuda", 0)
     torch.manual_seed(1234)
     r18 = a.backbone == "resnet18"
-    width, gflop = (512, R18_GFLOP_PER_TILE) if r18 else (2048, R50_GFLOP_PER_TILE)
-    enc = (resnet18 if r18 else retccl_resnet50)(chunk=a.chunk).to(dev).set_compute_dtype(torch.bfloat16)
+    simple = a.backbone == "simple"
+    width, gflop = (512, R18_GFLOP_PER_TILE) if r18 else (1024, SIMPLE_GFLOP_PER_TILE) if simple \
+        else (2048, R50_GFLOP_PER_TILE)
+    make = {"retccl": retccl_resnet50, "resnet18": resnet18, "simple": simple_cnn}[a.backbone]
+    enc = make(chunk=a.chunk).to(dev).set_compute_dtype(torch.bfloat16)
     enc.channels_last = a.layout == "nhwc"
     enc.train(a.encoder_mode == "train")
-    mil = TransMIL(2, width, 512).to(dev).train()
+    mil = (AttMIL(2, width, 512) if simple else TransMIL(2, width, 512)).to(dev).train()
     model = ImageBagModel(enc, mil)
     task = TransMILTask(mil)
     opt = task.configure_optimizers()[0][0]
@@ -139,8 +181,23 @@ def main():
     t_mil = timed(mil_step, a.steps)
     enc_tfs = gflop * a.n / t_enc / 1e3
     # the CPU oracle of the encoder is the ResNet-50's (oracle/encoder_ref.py): none for resnet18
-    cpu = cpu_baseline(a, enc, mil) if a.cpu_tiles > 0 and not r18 else None
+    cpu = cpu_baseline(a, enc, mil) if a.cpu_tiles > 0 and not r18 and not simple else None
     library = None
+    if simple and a.compare_library > 0:
+        lib_enc = LibrarySimple(enc)
+        ts = {"hand": [], "library": []}
+        with torch.no_grad():
+            err = (lib_enc(tiles[0][:64]) - enc(tiles[0][:64])).norm() / enc(tiles[0][:64]).norm()
+            lib_enc(tiles[0])                                                    # warm (MIOpen find)
+            for _ in range(a.compare_library):
+                for route, fn in (("hand", enc), ("library", lib_enc)):
+                    ts[route].append(timed(lambda: fn(tiles[0]), a.steps) * 1e3)
+        library = {"rounds": a.compare_library, "steps_per_round": a.steps,
+                   "encoder_ms_hand": [round(t, 3) for t in ts["hand"]],
+                   "encoder_ms_library": [round(t, 3) for t in ts["library"]],
+                   "rel_l2_library_vs_hand_64_tiles": float(err),
+                   "note": "same process, alternating; library = MIOpen 5x5 convolutions + torch ReLU / max-pool + "
+                           "the same split-K tm_gemm"}
     if r18 and a.compare_library > 0:
         hand = encoder_module._conv3x3
         ts = {"hand": [], "library": []}
@@ -157,24 +214,29 @@ def main():
                    "encoder_ms_hand": [round(t, 3) for t in ts["hand"]],
                    "encoder_ms_library": [round(t, 3) for t in ts["library"]],
                    "note": "same process, alternating; library = MIOpen 3x3 + tm_bias_act (+ torch add / ReLU)"}
-    name = "ResNet-18 encoder (fc 512) + TransMIL(512)" if r18 else "RetCCL ResNet-50 encoder + TransMIL(2048)"
+    name = "ResNet-18 encoder (fc 512) + TransMIL(512)" if r18 else "simple CNN encoder + AttMIL(1024)" if simple \
+        else "RetCCL ResNet-50 encoder + TransMIL(2048)"
+    net = "ResNet-18" if r18 else "simple CNN" if simple else "ResNet-50"
     print(json.dumps({
         "metric": f"slides/sec (fwd+bwd) end-to-end, {name}, N={a.n} tiles",
         "value": round(1.0 / t_step, 3), "unit": "slides/sec", "n_gpus": 1, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": round(t_step * 1e3, 3), "higher_is_better": True, "dtype": "bf16",
         "data": "synthetic (randn tiles resident in HBM, random-init weights)",
-        "config": {"workload": f"C5: 1 slide x {a.n} tiles 3x224x224 -> {'ResNet-18' if r18 else 'ResNet-50'} (frozen, BN "
-                               f"{'batch stats' if a.encoder_mode == 'train' else 'folded'}) -> TransMIL 2-class",
+        "config": {"workload": f"C5: 1 slide x {a.n} tiles 3x224x224 -> {net} (frozen, BN "
+                               f"{'none' if simple else 'batch stats' if a.encoder_mode == 'train' else 'folded'}) -> "
+                               f"{'AttMIL' if simple else 'TransMIL'} 2-class",
                    "execution": "hipGraph" if a.graph else "eager", "chunk": a.chunk, "layout": a.layout,
                    "miopen_find": a.benchmark, "backbone": a.backbone},
         "encoder": {"ms": round(t_enc * 1e3, 3), "tiles_per_s": round(a.n / t_enc, 1),
                     "achieved_tfs": round(enc_tfs, 1), "peak_tfs": BF16_PEAK_TFS,
                     "frac": round(enc_tfs / BF16_PEAK_TFS, 4), "mode": a.encoder_mode,
-                    "flops_note": f"{gflop} GFLOP per 224x224 tile ({'ResNet-18' if r18 else 'ResNet-50'} forward)"},
+                    "flops_note": f"{gflop} GFLOP per 224x224 tile ({net} forward)"},
         "mil_ms": round(t_mil * 1e3, 3),
         "roofline": {"bound": "mfma", "achieved": round(enc_tfs, 1), "peak": BF16_PEAK_TFS, "unit": "TFLOP/s",
                      "frac": round(enc_tfs / BF16_PEAK_TFS, 4), "traffic": None,
-                     "kernel": f"encoder ({a.encoder_mode} BN): hand-written stem (conv + BN + ReLU + pool, "
+                     "kernel": "encoder: two fused conv5x5 + ReLU + max-pool launches (tm_conv5x5_relu_pool), split-K "
+                               "tm_gemm + tm_bias_act Linear" if simple else
+                               f"encoder ({a.encoder_mode} BN): hand-written stem (conv + BN + ReLU + pool, "
                                "tm_stem_*), " + ("hand-written 3x3 implicit-GEMM convolutions (tm_conv3x3), " if r18
                                                  else "MIOpen / CK 3x3 convolutions, ") +
                                "hipBLASLt 1x1 GEMMs (tm_conv1x1), HIP BatchNorm / bias passes",

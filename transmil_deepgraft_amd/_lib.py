@@ -166,6 +166,7 @@ _SIGS = {
     "tm_conv1x1": (I, [I, P, P, P, P, P, L, I, I, I, P, L, P]),
     "tm_conv1x1_tune": (I, [I, P, P, P, P, P, L, I, I, I, P, L, P]),
     "tm_conv3x3": (I, [I, P, P, P, P, P, L, I, I, I, I, I, I, P]),
+    "tm_conv5x5_relu_pool": (I, [I, P, P, P, P, L, I, I, I, I, L, L, L, L, L, I, I, P]),
     "tm_bn_train_workspace": (L, [I]),
     "tm_bn_train_stats": (I, [I, P, P, I, I, P, P, P, P, Fl, Fl, P, P, P, L, P]),
     "tm_bn_apply": (I, [I, P, P, P, P, P, P, L, I, I, P]),

@@ -11,7 +11,8 @@ code/utils/utils.py:63-66, but with yaml.SafeLoader) and maps the keys `train.py
 * ``Model.backbone`` -> ``features`` runs on bags of features; ``retccl`` wraps the model in the
   on-GPU RetCCL encoder (``encoder.ImageBagModel``, model_interface.py:237-247, 300-316) and
   ``resnet18`` in the frozen ResNet-18 with its trainable 512 -> 512 ``fc`` (:226-234; the MIL
-  model then takes 512 features).
+  model then takes 512 features); ``simple`` in the MIL-AB tile CNN (``encoder.SimpleCNN``,
+  :270-281; 1024 features).
 * ``General.precision`` -> ``compute_dtype``: the reference's 16 / '16-mixed' (fp16 autocast)
   and 'bf16' / 'bf16-mixed' run the bf16 MFMA mode, 32 / '32-true' the fp32 parity mode.
 * ``Optimizer.opt / lr / weight_decay``, ``Loss.base_loss`` -> ``TransMILTask``;
@@ -45,13 +46,14 @@ def read_yaml(path) -> AttrDict:
 
 _FEATURE_WIDTH = {"retccl": 2048, "histoencoder": 384, "ctranspath": 784}
 _RESNET18_WIDTH = 512      # model_ft.fc = nn.Linear(512, 512) (model_interface.py:159, 234)
+_SIMPLE_WIDTH = 1024       # model_ft ends in Linear(53 * 53 * 50, 1024) + ReLU (model_interface.py:270-281)
 
 
 def _image_backbone(cfg):
     """The on-GPU tile encoder the config asks for (None: bags of features)."""
     if (cfg.Data or {}).get("feature_extractor") is not None:
         return None
-    return cfg.Model.backbone if cfg.Model.backbone in ("retccl", "resnet18") else None
+    return cfg.Model.backbone if cfg.Model.backbone in ("retccl", "resnet18", "simple") else None
 
 
 def compute_dtype_for(precision) -> torch.dtype:
@@ -74,14 +76,20 @@ def in_features_of(cfg) -> int:
             raise ValueError(f"Model.in_features {given} does not match backbone resnet18, whose output "
                              f"(fc = Linear(512, 512)) is {_RESNET18_WIDTH} wide")
         return _RESNET18_WIDTH
+    if _image_backbone(cfg) == "simple":
+        given = cfg.Model.in_features
+        if given is not None and int(given) != _SIMPLE_WIDTH:
+            raise ValueError(f"Model.in_features {given} does not match backbone simple, whose output "
+                             f"(Linear(140450, 1024) + ReLU) is {_SIMPLE_WIDTH} wide")
+        return _SIMPLE_WIDTH
     return int(cfg.Model.in_features or 1024)
 
 
 def build_model(cfg, device="cuda"):
     """``models.{Model.name}(n_classes, in_features, out_features)`` on the device, in the compute
-    dtype of ``General.precision``; wrapped in the RetCCL encoder for ``backbone: retccl`` and in
-    the ResNet-18 encoder for ``backbone: resnet18`` on images (``Model.backbone == 'features'``
-    keeps feature bags)."""
+    dtype of ``General.precision``; wrapped in the RetCCL encoder for ``backbone: retccl``, in the
+    ResNet-18 encoder for ``backbone: resnet18`` and in the MIL-AB tile CNN for ``backbone: simple``
+    on images (``Model.backbone == 'features'`` keeps feature bags)."""
     from . import models
     name = cfg.Model.name
     if not hasattr(models, name):
@@ -99,8 +107,9 @@ def build_model(cfg, device="cuda"):
         model.set_compute_dtype(dtype)
     backbone = _image_backbone(cfg)
     if backbone is not None:
-        from .encoder import ImageBagModel, resnet18, retccl_resnet50
-        enc = (retccl_resnet50 if backbone == "retccl" else resnet18)().to(device).set_compute_dtype(dtype)
+        from .encoder import ImageBagModel, resnet18, retccl_resnet50, simple_cnn
+        make = {"retccl": retccl_resnet50, "resnet18": resnet18, "simple": simple_cnn}[backbone]
+        enc = make().to(device).set_compute_dtype(dtype)
         model = ImageBagModel(enc, model)
     return model
 

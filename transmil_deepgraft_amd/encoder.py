@@ -36,6 +36,10 @@ Same module / parameter / buffer names as code/models/ResNet.py (ResNet :130-277
 It shares the controls, the stem and the forward scaffolding above (``_FrozenTileEncoder``); its 3x3
 convolutions -- all of its BasicBlocks -- run on the hand-written implicit-GEMM kernel
 (csrc/conv3x3.hip, 64-bit addressing) instead of the library.
+
+``SimpleCNN`` is the ``backbone: simple`` embedder of the ``AttMIL_simple_*`` configs
+(model_interface.py:270-281): two 5x5 convolution + ReLU + max-pool stages, each one launch of the
+hand-written kernel (csrc/conv5x5.hip), and Linear(140450, 1024) + ReLU on tm_gemm.
 """
 from __future__ import annotations
 
@@ -812,6 +816,196 @@ def resnet18(**kw):
     """torchvision ``resnet18`` as ``backbone: resnet18`` uses it (model_interface.py:226-234):
     frozen body, trainable ``fc = nn.Linear(512, 512)``."""
     return ResNet18(**kw)
+
+
+SIMPLE_CP = 24                       # channels per pixel between the two conv stages (20 + 4 zeros)
+SIMPLE_K = 50 * 53 * 53              # the Linear's fan-in: 140450
+SIMPLE_KP = 64 * 2195                # ... padded to whole 64-deep GEMM k-tiles: 140480
+
+
+def pack_conv5x5(w, dtype):
+    """Conv2d(3, 20, 5) / Conv2d(20, 50, 5) weights [cout, cin, 5, 5] -> tm_conv5x5_relu_pool's MFMA
+    fragment order [NS][NU][2][32][8] in ``dtype`` (include/transmil_hip.h): an 8-element fragment is
+    two adjacent kx taps x (3 channels + a zero) in the first stage (kx = 5 zero), 8 of a tap's
+    24 (20 + 4 zero) channels in the second; output channels padded to 32 / 64 zero rows."""
+    cout, cin = w.shape[0], w.shape[1]
+    if tuple(w.shape) not in ((20, 3, 5, 5), (50, 20, 5, 5)):
+        raise RuntimeError("pack_conv5x5: a [20, 3, 5, 5] or [50, 20, 5, 5] weight expected")
+    wt = w.detach().to(dtype).permute(0, 2, 3, 1)                      # [cout, ky, kx, cin]
+    if cin == 3:
+        nu, ns = 1, 8
+        full = torch.zeros(32, 5, 6, 4, dtype=dtype, device=w.device)
+        full[:cout, :, :5, :3] = wt
+    else:
+        nu, ns = 2, 38
+        full = torch.zeros(64, 25, 24, dtype=dtype, device=w.device)
+        full[:cout, :, :20] = wt.reshape(cout, 25, 20)
+    frags = torch.zeros(32 * nu, 2 * ns, 8, dtype=dtype, device=w.device)
+    nf = full[0].numel() // 8
+    frags[:, :nf] = full.reshape(32 * nu, nf, 8)
+    # [u][r][s][hf][j] -> [s][u][hf][r][j]
+    return frags.view(nu, 32, ns, 2, 8).permute(2, 0, 3, 1, 4).contiguous()
+
+
+def conv5x5_relu_pool(x, wp, bias, cout, out, so, cpo, tail=0):
+    """maxpool2x2/2(relu(conv5x5_valid(x) + bias)) on the hand-written kernel (tm_conv5x5_relu_pool)
+    into ``out`` (tile n at element n * so, ``cpo`` channels per pooled pixel, ``tail`` zeros after
+    each tile's pixels).  x: [n, 3, h, w] tiles at any strides (cout 20), or the first stage's
+    [n, h, w, 24] channels-last output (cout 50)."""
+    from . import _lib
+    from .engine import _p, _stream
+    if x.dtype != wp.dtype or x.dtype != out.dtype or bias.dtype != torch.float32:
+        raise RuntimeError("conv5x5: x, packed weights and out of one dtype and an fp32 bias expected")
+    if cout == 20:
+        n, cin, h, w = x.shape
+        sn, sc, sh, sw = x.stride()
+    else:
+        n, h, w, cin = x.shape
+        sn, sh, sw, sc = x.stride()
+        cin = 20 if cin == SIMPLE_CP else -1
+    _lib.call("tm_conv5x5_relu_pool", _dtype_code(x), _p(x), _p(wp), _p(bias), _p(out), n, h, w, cin, cout,
+              sn, sc, sh, sw, so, cpo, tail, _stream())
+    return out
+
+
+def pack_simple_fc(w, dtype):
+    """Linear(140450, width) weight from the reference's NCHW flatten order (c, y, x) to the order the
+    second conv stage writes (y, x, c), K zero-padded to SIMPLE_KP, in ``dtype``."""
+    width = w.shape[0]
+    wp = torch.zeros(width, SIMPLE_KP, dtype=dtype, device=w.device)
+    wp[:, :SIMPLE_K] = w.detach().view(width, 50, 53, 53).permute(0, 2, 3, 1).reshape(width, SIMPLE_K)
+    return wp
+
+
+def simple_fc(a, wp, bias, out):
+    """out[m, :] = relu(a[m, :] . wp^T + bias) over the K-padded feature rows ``a`` [m, SIMPLE_KP]:
+    tm_gemm as a split-K product (fp32 slabs, summed in split order: deterministic), then bias + ReLU
+    in one in-place pass (tm_bias_act).  The splits fill the device at small m and keep every fp32
+    accumulation chain short (K = 140480 in one chain is what the parity mode cannot afford)."""
+    from . import _lib
+    from ._lib import EPI_SPLITK, F32, GemmArgs
+    from .engine import _p, _stream, cu_count
+    import ctypes as C
+    m, n = a.shape[0], wp.shape[0]
+    if a.shape[1] != SIMPLE_KP or wp.shape[1] != SIMPLE_KP or not a.is_contiguous() or not wp.is_contiguous() or \
+            a.dtype != wp.dtype or out.dtype != torch.float32 or not out.is_contiguous() or n % 8:
+        raise RuntimeError("simple_fc: contiguous [m, 140480] rows and [width, 140480] weights of one dtype, "
+                           "fp32 contiguous out, width % 8 == 0 expected")
+    tiles = ((m + 127) // 128) * ((n + 127) // 128)
+    kt = SIMPLE_KP // 64
+    splits = max(1, min(64, (2 * cu_count()) // tiles))
+    kps = -(-kt // splits) * 64
+    splits = -(-SIMPLE_KP // kps)
+    slab = torch.empty(splits, m, n, dtype=torch.float32, device=a.device)
+    g = GemmArgs()
+    g.M, g.N, g.K = m, n, SIMPLE_KP
+    g.lda, g.ldb, g.ldc = SIMPLE_KP, SIMPLE_KP, n
+    g.ab_dtype, g.c_dtype = _dtype_code(a), F32
+    g.splits, g.k_per_split = splits, kps
+    g.mode = EPI_SPLITK
+    g.alpha = 1.0
+    _lib.call("tm_gemm", _p(a), _p(wp), _p(slab), C.byref(g), _stream())
+    _lib.call("tm_splitk_reduce", _p(slab), _p(out), splits, m * n, C.c_float(1.0), 0, None, _stream())
+    _lib.call("tm_bias_act", F32, _p(out), _p(bias), m, n, 1, _stream())
+    return out
+
+
+class SimpleCNN(nn.Module):
+    """``Model.backbone: simple`` (model_interface.py:270-281), the MIL-AB tile embedder
+    ``Sequential(Conv2d(3, 20, 5), ReLU, MaxPool2d(2, 2), Conv2d(20, 50, 5), ReLU, MaxPool2d(2, 2),
+    View(-1, 50 * 53 * 53), Linear(140450, 1024), ReLU)``: tiles [n, 3, 224, 224] -> [n, width] fp32.
+    The parameterised layers sit at the Sequential's indices (state_dict keys ``0.*``, ``3.*``,
+    ``7.*``), so a checkpoint's ``model_ft.*`` tensors load unchanged.
+
+    Each conv stage (convolution + bias + ReLU + pool) is one tm_conv5x5_relu_pool launch; the second
+    writes the rows of the Linear's A matrix directly ((y, x, c) order, K padded to 140480 with
+    zeros), and the Linear is a split-K tm_gemm + tm_bias_act.  No BatchNorm, no dropout: train and
+    eval mode compute the same function.  The parameters are frozen and the forward runs without
+    autograd: the reference's optimizer is built from the MIL model alone (:862-877), so these
+    weights never change there either -- only the unused backward is gone."""
+
+    _name = "simple CNN encoder"
+
+    def __init__(self, width=1024, chunk=512):
+        super().__init__()
+        if width % 8:
+            raise ValueError("SimpleCNN: width must be a multiple of 8")
+        self.add_module("0", nn.Conv2d(3, 20, kernel_size=5))
+        self.add_module("3", nn.Conv2d(20, 50, kernel_size=5))
+        self.add_module("7", nn.Linear(SIMPLE_K, width))
+        self.width = width
+        self.compute_dtype = torch.bfloat16
+        self.chunk = chunk
+        self._folded = None
+        self._folded_key = None
+        for p in self.parameters():
+            p.requires_grad = False
+
+    def set_compute_dtype(self, dtype):
+        if dtype not in (torch.bfloat16, torch.float32):
+            raise ValueError("compute dtype must be torch.bfloat16 or torch.float32")
+        self.compute_dtype = dtype
+        self._folded = None
+        return self
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        self._folded = None
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
+
+    def load_lightning_state_dict(self, state_dict, prefix="model_ft."):
+        """Load the ``model_ft.``-prefixed tensors of a Lightning checkpoint's state dict (the only
+        way to reproduce a trained run's features: the reference never updates them, so they are its
+        initial values)."""
+        sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        return self.load_state_dict(sd, strict=True)
+
+    def _fold_key(self):
+        """Identity of every parameter the packed weights derive from (storage and in-place version
+        counter): ``.to()``, a checkpoint load or an in-place edit change it and the next forward
+        packs again."""
+        return tuple((p.data_ptr(), p._version, p.dtype) for p in self.parameters()) + (self.compute_dtype,)
+
+    def _fold_all(self):
+        dt = self.compute_dtype
+        m = dict(self.named_children())
+        self._folded = {
+            "w1": pack_conv5x5(m["0"].weight, dt), "b1": m["0"].bias.detach().float().contiguous(),
+            "w2": pack_conv5x5(m["3"].weight, dt), "b2": m["3"].bias.detach().float().contiguous(),
+            "wfc": pack_simple_fc(m["7"].weight, dt), "bfc": m["7"].bias.detach().float().contiguous(),
+        }
+
+    def forward(self, x):
+        if x.dim() != 4 or x.shape[1] != 3 or tuple(x.shape[2:]) != (224, 224):
+            raise RuntimeError(f"{self._name}: tiles must be [n, 3, 224, 224] (the Linear fixes the 53 x 53 x 50 "
+                               f"feature map); got {tuple(x.shape)}")
+        if not x.is_cuda:
+            raise RuntimeError(f"{self._name} (MI355X path) needs a GPU tensor")
+        dt = self.compute_dtype
+        with torch.no_grad():
+            key = self._fold_key()
+            if self._folded is None or self._folded_key != key:
+                self._fold_all()
+                self._folded_key = key
+            f = self._folded
+            out = torch.empty(x.shape[0], self.width, dtype=torch.float32, device=x.device)
+            # the GEMM's A matrix stays under 2^31 bytes
+            chunk = max(1, min(self.chunk, (2 ** 31 - 1) // (SIMPLE_KP * (2 if dt == torch.bfloat16 else 4))))
+            for s in range(0, x.shape[0], chunk):
+                xc = x[s:s + chunk].to(dt)                 # read at its own strides: no layout copy
+                nc = xc.shape[0]
+                y1 = torch.empty(nc, 110, 110, SIMPLE_CP, dtype=dt, device=x.device)
+                conv5x5_relu_pool(xc, f["w1"], f["b1"], 20, y1, 110 * 110 * SIMPLE_CP, SIMPLE_CP)
+                a = torch.empty(nc, SIMPLE_KP, dtype=dt, device=x.device)
+                conv5x5_relu_pool(y1, f["w2"], f["b2"], 50, a, SIMPLE_KP, 50, SIMPLE_KP - SIMPLE_K)
+                del y1
+                simple_fc(a, f["wfc"], f["bfc"], out[s:s + nc])
+        return out
+
+
+def simple_cnn(**kw):
+    """The ``simple`` backbone of the reference's ``AttMIL_simple_*.yaml`` configs
+    (model_interface.py:270-281), frozen."""
+    return SimpleCNN(**kw)
 
 
 class ImageBagModel(nn.Module):
