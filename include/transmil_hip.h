@@ -396,6 +396,21 @@ int tm_attmil_bwd(const float* Z, const float* H, const float* w, const float* p
 int tm_gather_rows(int dtype, const void* src, int F, const long long* i0, const long long* i1,
                    const float* wa, const float* wb, int nrows, void* dst, void* stream);
 
+/* ---- tile-bag ingest (tiles.hip) -- code/datasets/jpg_dataloader.py:164-171, 229-293 ----
+ * dst[r][c][h][w] = lut[c][src[idx[r]][h][w][c]] rounded to dtype (ToTensor + Normalize as a
+ * [3][256] fp32 table the caller computes), or an all-zero tile where idx[r] < 0 or >= ntiles
+ * (to_fixed_size_bag's zero padding; an index can never read outside the slab).  src is a uint8
+ * slab [ntiles][H][W][3] (tile t at byte t*H*W*3, a tile < 2 GiB), idx int64 [n] and lut on the
+ * device, dst of dtype TM_F32 / TM_BF16 addressed by the element strides dn, dc, dh, dw (> 0:
+ * NCHW, channels-last or any other non-overlapping layout).  64-bit addressing throughout; any
+ * n < 2^31 in one launch; n == 0 returns 0 without a launch.  Dword loads and 16-B stores where W
+ * is a multiple of 16 B / sizeof(dtype), src is 4-B and dst 16-B aligned and the strides are those
+ * of planes (dw == 1) or of channels-last pixels (dc == 1, dw == 3) with 16-B-aligned rows; the
+ * same bits otherwise. */
+int tm_gather_tiles_u8(int dtype, const void* src, long long ntiles, int H, int W, const long long* idx,
+                       long long n, const float* lut, void* dst, long long dn, long long dc, long long dh,
+                       long long dw, void* stream);
+
 /* ---- glue (glue.hip) -- code/models/TransMIL.py:177-186 ------------------ */
 int tm_put_cls(const float* cls, int B, int S, int D, float* H, void* stream);
 /* CrossEntropyLoss(logits, one_hot(label).float()) mean over B rows + softmax + argmax in one

@@ -140,6 +140,7 @@ _SIGS = {
     "tm_ppeg_bwd_workspace": (L, [I, I, I]),
     "tm_ppeg_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P, P, I, P, I, I, Fl, U64, P, P, P]),
     "tm_gather_rows": (I, [I, P, I, P, P, P, P, I, P, P]),
+    "tm_gather_tiles_u8": (I, [I, P, L, I, I, P, L, P, P, L, L, L, L, P]),
     "tm_attmil_fwd_workspace": (L, [I, I]),
     "tm_attmil_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
     "tm_attmil_bwd_workspace": (L, [I, I, I]),

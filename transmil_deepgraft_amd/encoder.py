@@ -81,6 +81,11 @@ def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d, dtype, cl=True):
     return w.contiguous(memory_format=torch.channels_last if cl else torch.contiguous_format), b
 
 
+def _is_tile_bag(x):
+    from .data import TileBag
+    return isinstance(x, TileBag)
+
+
 def _dtype_code(t):
     from ._lib import BF16, F32
     if t.dtype not in (torch.bfloat16, torch.float32):
@@ -491,7 +496,9 @@ class _FrozenTileEncoder(nn.Module):
         if not x.is_cuda:
             raise RuntimeError(f"{self._name} (MI355X path) needs a GPU tensor")
         dt = self.compute_dtype
-        out = torch.empty(x.shape[0], self.width, dtype=torch.float32, device=x.device)
+        lazy = _is_tile_bag(x)           # a data.TileBag: gathered chunk by chunk in the compute dtype
+        n, th, tw = (x.n_tiles, x.shape[3], x.shape[4]) if lazy else (x.shape[0], x.shape[2], x.shape[3])
+        out = torch.empty(n, self.width, dtype=torch.float32, device=x.device)
         if not self.training:
             key = self._fold_key()
             if self._folded is None or self._folded_key != key:
@@ -508,21 +515,28 @@ class _FrozenTileEncoder(nn.Module):
         # autocast keeps fp32 BatchNorm outputs: sized as fp32).
         fused_train = self.training and not grad and self.channels_last
         esz = 2 if dt == torch.bfloat16 and (fused_train or not self.training) else 4
-        cap = max_tiles_per_call(x.shape[2], x.shape[3], esz)
-        chunk = x.shape[0] if self.training else max(1, min(self.chunk, cap))
-        if self.training and not fused_train and x.shape[0] > cap:
+        cap = max_tiles_per_call(th, tw, esz)
+        chunk = n if self.training else max(1, min(self.chunk, cap))
+        if self.training and not fused_train and n > cap:
             # nn.BatchNorm2d needs the whole batch in one module call; above the cap that call
             # would hand the library > 2^31-element tensors
             raise RuntimeError(f"encoder: train mode with autograd (or without channels-last) takes at most {cap} "
                                f"tiles per call (the whole-batch BatchNorm would hand the library >= 2^31 bytes); got "
-                               f"{x.shape[0]}")
+                               f"{n}")
         autocast = self.training and not fused_train and dt == torch.bfloat16
+        # (the fused stem reads the tiles at any strides: no channels-last copy)
+        any_strides = (not self.training or fused_train) and self.channels_last and dt == torch.bfloat16 \
+            and _stem_fused_enabled()
         with torch.set_grad_enabled(grad), torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
-            for s in range(0, x.shape[0], chunk):
-                xc = x[s:s + chunk].to(torch.float32 if autocast else dt)
-                if not ((not self.training or fused_train) and self.channels_last and dt == torch.bfloat16
-                        and _stem_fused_enabled()):
-                    # (the fused stem reads the tiles at any strides: no channels-last copy)
+            for s in range(0, n, chunk):
+                if lazy:
+                    # one gather per chunk, in the layout the stem wants (train mode: chunk = the whole
+                    # bag, materialised once in the compute dtype for the whole-bag statistics)
+                    xc = x.tiles(s, s + chunk, torch.float32 if autocast else dt,
+                                 "nhwc" if self.channels_last and not any_strides else "nchw")
+                else:
+                    xc = x[s:s + chunk].to(torch.float32 if autocast else dt)
+                if not any_strides:
                     xc = xc.contiguous(memory_format=torch.channels_last if self.channels_last
                                        else torch.contiguous_format)
                 if not self.training:
@@ -975,11 +989,13 @@ class SimpleCNN(nn.Module):
         }
 
     def forward(self, x):
-        if x.dim() != 4 or x.shape[1] != 3 or tuple(x.shape[2:]) != (224, 224):
+        lazy = _is_tile_bag(x)           # a data.TileBag: gathered chunk by chunk in the compute dtype
+        if tuple(x.shape[-3:]) != (3, 224, 224) or (not lazy and x.dim() != 4):
             raise RuntimeError(f"{self._name}: tiles must be [n, 3, 224, 224] (the Linear fixes the 53 x 53 x 50 "
                                f"feature map); got {tuple(x.shape)}")
         if not x.is_cuda:
             raise RuntimeError(f"{self._name} (MI355X path) needs a GPU tensor")
+        n = x.n_tiles if lazy else x.shape[0]
         dt = self.compute_dtype
         with torch.no_grad():
             key = self._fold_key()
@@ -987,11 +1003,12 @@ class SimpleCNN(nn.Module):
                 self._fold_all()
                 self._folded_key = key
             f = self._folded
-            out = torch.empty(x.shape[0], self.width, dtype=torch.float32, device=x.device)
+            out = torch.empty(n, self.width, dtype=torch.float32, device=x.device)
             # the GEMM's A matrix stays under 2^31 bytes
             chunk = max(1, min(self.chunk, (2 ** 31 - 1) // (SIMPLE_KP * (2 if dt == torch.bfloat16 else 4))))
-            for s in range(0, x.shape[0], chunk):
-                xc = x[s:s + chunk].to(dt)                 # read at its own strides: no layout copy
+            for s in range(0, n, chunk):
+                # read at its own strides: no layout copy
+                xc = x.tiles(s, s + chunk, dt) if lazy else x[s:s + chunk].to(dt)
                 nc = xc.shape[0]
                 y1 = torch.empty(nc, 110, 110, SIMPLE_CP, dtype=dt, device=x.device)
                 conv5x5_relu_pool(xc, f["w1"], f["b1"], 20, y1, 110 * 110 * SIMPLE_CP, SIMPLE_CP)
@@ -1022,5 +1039,6 @@ class ImageBagModel(nn.Module):
 
     def forward(self, x):
         B, bag = x.shape[0], x.shape[1]
-        feats = self.model_ft(x.reshape(B * bag, *x.shape[2:]))
+        # a lazy data.TileBag goes to the encoder as it is: it stands for the flattened [B * bag] tiles
+        feats = self.model_ft(x if _is_tile_bag(x) else x.reshape(B * bag, *x.shape[2:]))
         return self.model(feats.view(B, bag, -1))

@@ -836,6 +836,23 @@ class _EvalState:
         self.names, self.patients = [], []
 
 
+def _is_tile_bag(bags):
+    from .data import TileBag
+    return isinstance(bags, TileBag)
+
+
+def _model_input(bags):
+    """What the model is called with: a tensor batch as fp32 contiguous; a lazy ``data.TileBag`` as
+    it is (the encoder gathers it chunk by chunk in its compute dtype: no float bag here)."""
+    return bags if _is_tile_bag(bags) else bags.float().contiguous()
+
+
+def _refuse_tile_bag(who, bags):
+    if _is_tile_bag(bags):
+        raise TypeError(f"{who}: a lazy TileBag cannot be captured (its gathers are issued per chunk by the "
+                        "encoder); pass materialize()d tiles, or run the eager step")
+
+
 class TransMILTask(nn.Module):
     """``ModelInterface`` training / validation / test step subset for the feature-bag path."""
 
@@ -857,7 +874,7 @@ class TransMILTask(nn.Module):
         return self.model(x)
 
     def step(self, bags):
-        logits = self(bags.float().contiguous())
+        logits = self(_model_input(bags))
         y_hat = torch.argmax(logits, dim=1)
         y_prob = F.softmax(logits, dim=1)
         return logits, y_prob, y_hat
@@ -867,7 +884,7 @@ class TransMILTask(nn.Module):
         if bags.is_cuda and isinstance(self.loss, nn.CrossEntropyLoss):
             # fused: loss, Y_prob, Y_hat and the per-class count/correct of :350-356 in one launch --
             # the head's own launch where the model offers it (TransMIL.forward_ce), else tm_ce_fwd
-            x = bags.float().contiguous()
+            x = _model_input(bags)
             if self.class_stats is None or self.class_stats.device != x.device:
                 self.class_stats = torch.zeros(self.n_classes, 2, dtype=torch.int32, device=x.device)
             fused = getattr(self.model, "forward_ce", None)
@@ -957,7 +974,9 @@ class TransMILTask(nn.Module):
         names, patients = meta[0], meta[-1]
         from .encoder import ImageBagModel
         nd = 5 if isinstance(self.model, ImageBagModel) else 3      # tile bags [B, N, 3, H, W]
-        if bags.dim() == nd - 1:
+        if _is_tile_bag(bags):
+            pass                                                    # always [B, bag, 3, H, W]
+        elif bags.dim() == nd - 1:
             bags = bags.unsqueeze(0)
         elif bags.dim() > nd:
             bags = bags.squeeze(0)
@@ -979,7 +998,7 @@ class TransMILTask(nn.Module):
         """The device side of an evaluation step: the forward (the model in whatever mode it is in,
         under no_grad) and the record launch.  This is what ``GraphedEvaluation`` captures."""
         with torch.no_grad():
-            logits = self(bags.float().contiguous())
+            logits = self(_model_input(bags))
             record.write(logits.float().contiguous(), label)
         return logits
 
@@ -987,7 +1006,7 @@ class TransMILTask(nn.Module):
         bags, label, names, patients = self._parse_eval_batch(batch)
         st = self.eval_state(stage, bags.device)
         with torch.no_grad():
-            logits = self(bags.float().contiguous())
+            logits = self(_model_input(bags))
             st.record.append(logits, label.to(device=logits.device, dtype=torch.int64))
         st.names += names            # names stay on the host, in append order
         st.patients += patients
@@ -1191,6 +1210,7 @@ class GraphedOptimizationStep:
         if getattr(self, "_closed", False):
             raise RuntimeError("GraphedOptimizationStep: called after close()")
         bags, label = batch[0], batch[1]
+        _refuse_tile_bag("GraphedOptimizationStep", bags)
         task = self.task
         if self.graphs is None:
             if self.shape is None:
@@ -1272,6 +1292,7 @@ class GraphedEvaluation:
         return len(self.graphs)
 
     def __call__(self, batch, batch_idx=None):
+        _refuse_tile_bag("GraphedEvaluation", batch[0])
         if self._closed:
             raise RuntimeError("GraphedEvaluation: called after close()")
         task, st = self.task, self.state
