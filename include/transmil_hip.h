@@ -81,7 +81,26 @@ typedef struct tm_gemm_args {
 } tm_gemm_args;
 
 int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args* args, void* stream);
-/* Deferred parameter-gradient reductions.  A tm_reduce_queue is a caller-owned host object
+/* Two independent products as ONE launch.  Between tm_gemm_pair_begin(stream) and
+ * tm_gemm_pair_end(stream) the calling thread's tm_gemm calls on that stream (two at most) are
+ * checked as usual but only held (pointers and a copy of the arguments: the caller keeps owning
+ * every buffer, which must stay valid until `end` returns); `end` launches them.  A bf16 split-K
+ * weight gradient (a_trans = b_kn = 1, TM_EPI_SPLITK) and a bf16 plain data gradient (a_trans = 0,
+ * b_kn = 1, no split, plain epilogue), in either call order, both on the 128 x 128 ring (K and
+ * k_per_split multiples of 64, the k-strided extents multiples of 8), run as one grid of the same
+ * tiles: every output bit-identical to the separate launches.  Anything else held (one call, a
+ * shape off the ring, fp32 operands, another epilogue) is launched separately in call order; no
+ * call held: `end` does nothing.  The caller asserts that neither product reads the other's output,
+ * and issues nothing else that launches on `stream` between begin and end (reductions deferred to a
+ * tm_reduce_queue are fine: they launch at the flush).
+ * The held state is host-side and per calling THREAD (one open pair per thread, bound to the stream
+ * given to begin; tm_gemm calls on other streams launch at once).  An error at begin (a pair already
+ * open), at a held tm_gemm (bad arguments, a third call) or at end (another stream) closes the pair
+ * and drops what was held: nothing stays held after a non-zero return, and an `end` that finds no
+ * open pair returns 0.  No device state, no synchronisation: capturable like tm_gemm. */
+int tm_gemm_pair_begin(void* stream);
+int tm_gemm_pair_end(void* stream);
+/* Deferred parameter-gradient reductions. A tm_reduce_queue is a caller-owned host object
  * (no device memory, no stream): every entry point below that ends in a split-K / slab sum takes
  * `tm_reduce_queue* rq`.  rq == NULL launches the sum now on `stream`; otherwise the (slab, out)
  * pair is only appended to *rq, and tm_reduce_flush(rq, stream) sums every queued pair in ONE

@@ -67,6 +67,8 @@ _SIGS = {
     "tm_last_error": (C.c_char_p, []),
     "tm_build_info": (C.c_char_p, []),
     "tm_gemm": (I, [P, P, P, C.POINTER(GemmArgs), P]),
+    "tm_gemm_pair_begin": (I, [P]),
+    "tm_gemm_pair_end": (I, [P]),
     "tm_splitk_reduce": (I, [P, P, I, L, Fl, I, P, P]),
     "tm_splitk_reduce_bf16": (I, [P, P, I, L, Fl, I, P, P]),
     "tm_colsum_workspace": (L, [I, I, I]),

@@ -655,18 +655,20 @@ TM_DEV void ring_stamp(unsigned long long (&ts)[8], int slot, bool real = false)
   }
 }
 
-template <typename OutT, bool A_T, bool B_KN, bool STAMP = false, int KIND = EK_ANY>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void gemm_ring_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
-                                                        OutT* __restrict__ C, tm_gemm_args g) {
+// One 128 x 128 tile (rows m0.., columns n0.., split zs) of the ring GEMM: the whole workgroup's work,
+// shared by the plain launch (gemm_ring_kernel: tile from blockIdx) and the paired launch
+// (gemm_ring_pair_kernel: job and tile decoded from the linear block id).
+// `tid` is the caller's threadIdx.x, read in the __global__ where it carries the launch bounds' range.
+template <typename OutT, bool A_T, bool B_KN, bool STAMP, int KIND>
+TM_DEV void gemm_ring_tile(const bf16* A, const bf16* B, OutT* C, const tm_gemm_args& g, const int tid,
+                           const int m0, const int n0, const int zs) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   ring_stamp<STAMP>(ts, 0, true);
   ring_stamp<STAMP>(ts, 1);
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;  // 4 (M) x 2 (N) waves of 32 x 64
-  int m0, n0, zs;
-  tile_split_of_block(m0, n0, zs);
   const int kbeg = zs * g.k_per_split;
   const int kend = min(g.K, kbeg + g.k_per_split);
   const int nk = kend > kbeg ? (kend - kbeg) / 64 : 0;  // host guarantees 64 | (kend - kbeg)
@@ -774,6 +776,72 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void g
       for (int i = 1; i < 8; ++i) v = tid == i ? ts[i] : v;
       g_gemm_stamps[blk * 8 + tid] = v;
     }
+  }
+}
+
+template <typename OutT, bool A_T, bool B_KN, bool STAMP = false, int KIND = EK_ANY>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void gemm_ring_kernel(const bf16* __restrict__ A, const bf16* __restrict__ B,
+                                                        OutT* __restrict__ C, tm_gemm_args g) {
+  int m0, n0, zs;
+  tile_split_of_block(m0, n0, zs);
+  gemm_ring_tile<OutT, A_T, B_KN, STAMP, KIND>(A, B, C, g, threadIdx.x, m0, n0, zs);
+}
+
+// ---------------------------------------------------------------------------
+// Paired launch: a split-K weight gradient (job W: k-strided A and B, fp32 / bf16 slabs) and the data
+// gradient of the same dY (job D: k-contiguous A, B as [K, N], plain bf16 store) as ONE grid of
+// 128 x 128 ring tiles.  The two products are independent; in one launch the D tiles' HBM-bound
+// epilogues run under the W tiles' long k-loops, and the step has one dependent launch boundary less.
+// Every tile is computed by gemm_ring_tile exactly as in the plain launch (bit-identical outputs).
+//
+// Block order: the hardware deals linear block ids round-robin over the 8 XCDs, so blocks are taken in
+// groups of 8 (one per XCD) and whole groups go to one job; inside a job the group index and the XCD
+// give the job-local id that tile_split_of_block's XCD-contiguous renumbering expects (a job whose
+// block count is no multiple of 8 leaves the tail of its last group idle).  PAIR_INTERLEAVED deals the
+// groups to the two jobs in proportion to their sizes (each CU's two resident workgroups tend to be
+// one of each); PAIR_W_FIRST puts every W group ahead of the D groups.
+enum { PAIR_INTERLEAVED = 0, PAIR_W_FIRST = 1 };
+struct PairGrid {
+  int nw, nd;        // workgroups of job W (tiles x splits) and of job D (tiles)
+  int gw, gd;        // groups of 8: ceil(nw / 8), ceil(nd / 8)
+  int ntx_w, per_w;  // job W: column tiles, tiles per split
+  int ntx_d;         // job D: column tiles
+};
+
+// XCD-contiguous renumbering of job-local block `orig` of `nwg` (tile_split_of_block's map)
+TM_DEV int xcd_contiguous_id(int orig, int nwg) {
+  const int q = nwg / 8, r = nwg % 8, xcd = orig % 8;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void gemm_ring_pair_kernel(
+    const bf16* __restrict__ Aw, const bf16* __restrict__ Bw, float* __restrict__ Cw, tm_gemm_args gw,
+    const bf16* __restrict__ Ad, const bf16* __restrict__ Bd, bf16* __restrict__ Cd, tm_gemm_args gd, PairGrid p) {
+  const int grp = blockIdx.x >> 3, x = blockIdx.x & 7;
+  const int groups = p.gw + p.gd;
+  // W groups among the first grp groups, and whether group grp is one
+  int wbefore, is_w;
+  if (ORDER == PAIR_W_FIRST) {
+    wbefore = min(grp, p.gw);
+    is_w = grp < p.gw;
+  } else {
+    wbefore = (int)((long long)grp * p.gw / groups);
+    is_w = (int)((long long)(grp + 1) * p.gw / groups) > wbefore;
+  }
+  if (is_w) {   // block-uniform
+    const int orig = wbefore * 8 + x;
+    if (orig >= p.nw) return;
+    const int id = xcd_contiguous_id(orig, p.nw);
+    const int zs = id / p.per_w, rr = id - zs * p.per_w;
+    gemm_ring_tile<float, true, true, false, EK_SPLITK>(Aw, Bw, Cw, gw, threadIdx.x, (rr / p.ntx_w) * BM,
+                                                        (rr % p.ntx_w) * BN, zs);
+  } else {
+    const int orig = (grp - wbefore) * 8 + x;
+    if (orig >= p.nd) return;
+    const int id = xcd_contiguous_id(orig, p.nd);
+    gemm_ring_tile<bf16, false, true, false, EK_PLAIN>(Ad, Bd, Cd, gd, threadIdx.x, (id / p.ntx_d) * BM,
+                                                       (id % p.ntx_d) * BN, 0);
   }
 }
 
@@ -1283,9 +1351,60 @@ __global__ void colsum_partial_kernel(const T* __restrict__ X, int rows, int col
     part[(size_t)blockIdx.y * cols + c] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-}  // namespace
+// ---- paired launches (tm_gemm_pair_begin / tm_gemm_pair_end): host-side state only, per calling
+// thread: the stream of the open pair and the (up to two) validated tm_gemm calls held for it.
+struct HeldGemm {
+  const void* A;
+  const void* B;
+  void* C;
+  tm_gemm_args g;
+};
+struct PairState {
+  bool open = false;
+  void* stream = nullptr;
+  int n = 0;
+  HeldGemm h[2];
+};
+thread_local PairState t_pair;
 
-extern "C" int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args* g, void* stream) {
+// Block order of the paired launch, fixed by measurement: weight-gradient blocks first ran the step
+// 0.3 % ahead of the interleaved order in every trio of profiles/r09a_ab_pair_orders.txt (the long
+// k-loops start first and the data gradient's tiles fill in beside them)
+constexpr int PAIR_ORDER = PAIR_W_FIRST;
+
+// the two roles of the instantiated pair: split-K weight gradient / plain data gradient, both on the
+// 128 x 128 ring, bf16 operands
+inline bool pair_w_ok(const tm_gemm_args& g) {
+  return g.ab_dtype == TM_BF16 && g.c_dtype == TM_F32 && g.a_trans == 1 && g.b_kn == 1 && g.mode == TM_EPI_SPLITK &&
+         ring_ok(g);
+}
+inline bool pair_d_ok(const tm_gemm_args& g) {
+  return g.ab_dtype == TM_BF16 && g.c_dtype == TM_BF16 && g.a_trans == 0 && g.b_kn == 1 && g.splits == 1 &&
+         epilogue_kind(g) == EK_PLAIN && ring_ok(g);
+}
+
+int launch_pair(const HeldGemm& w, const HeldGemm& d, hipStream_t st) {
+  PairGrid p;
+  p.ntx_w = (w.g.N + BN - 1) / BN;
+  p.per_w = p.ntx_w * ((w.g.M + BM - 1) / BM);
+  p.nw = p.per_w * w.g.splits;
+  p.ntx_d = (d.g.N + BN - 1) / BN;
+  p.nd = p.ntx_d * ((d.g.M + BM - 1) / BM);
+  p.gw = (p.nw + 7) / 8;
+  p.gd = (p.nd + 7) / 8;
+  constexpr size_t epi = (size_t)BM * EP_ROW * sizeof(float);
+  constexpr size_t lds = RING_BYTES > epi ? RING_BYTES : epi;
+  auto kernel = gemm_ring_pair_kernel<PAIR_ORDER>;
+  tm_allow_smem(kernel, lds);
+  kernel<<<dim3((unsigned)(p.gw + p.gd) * 8), 512, lds, st>>>((const bf16*)w.A, (const bf16*)w.B, (float*)w.C, w.g,
+                                                               (const bf16*)d.A, (const bf16*)d.B, (bf16*)d.C, d.g, p);
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+// argument checks of tm_gemm (no launch); *empty: nothing to compute
+int gemm_check(const void* A, const void* B, void* C, const tm_gemm_args* g, bool* empty) {
+  *empty = false;
   TM_REQUIRE(g && A && B && C, "gemm: null argument");
   TM_REQUIRE(g->M >= 0 && g->N >= 0 && g->K >= 0 && g->splits >= 1, "gemm: bad shape");
   TM_REQUIRE(g->mode != TM_EPI_SPLITK || g->c_dtype == TM_F32, "gemm: split-K slabs are fp32 (or bf16 via slab_bf16)");
@@ -1296,21 +1415,83 @@ extern "C" int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args
   const int E = g->ab_dtype == TM_BF16 ? 8 : 4;
   TM_REQUIRE(g->lda % E == 0 && g->ldb % E == 0, "gemm: leading dimensions must be multiples of 16 B");
   TM_REQUIRE(g->mode != TM_EPI_QKV || (g->dh % 8 == 0 && g->N % 8 == 0), "gemm: QKV scatter needs dh % 8 == 0");
-  if (g->M == 0 || g->N == 0) return 0;
+  if (g->M == 0 || g->N == 0) {
+    *empty = true;
+    return 0;
+  }
   // the fused bias-gradient column sums ride in the bf16 ring kernel's split-K weight-gradient form only
   TM_REQUIRE(!g->colsum || (g->ab_dtype == TM_BF16 && g->c_dtype == TM_F32 && g->a_trans && g->mode == TM_EPI_SPLITK &&
                             pick_path(*g) == PATH_RING && GEMM_SEL != GEMM_STAMP_RING),
              "gemm: colsum needs the bf16 split-K weight-gradient ring path (a_trans, K % 64 == 0, M % 8 == 0)");
-  hipStream_t st = (hipStream_t)stream;
   if (g->ab_dtype == TM_BF16) {
     TM_REQUIRE(g->k_per_split % 64 == 0 || g->splits == 1, "gemm: bf16 k_per_split must be a multiple of 64");
-    if (g->c_dtype == TM_BF16) return launch_t<bf16, bf16>(A, B, C, *g, st);
-    return launch_t<bf16, float>(A, B, C, *g, st);
+    return 0;
   }
   TM_REQUIRE(g->ab_dtype == TM_F32, "gemm: ab_dtype");
   TM_REQUIRE(g->k_per_split % 32 == 0 || g->splits == 1, "gemm: f32 k_per_split must be a multiple of 32");
-  if (g->c_dtype == TM_BF16) return launch_t<float, bf16>(A, B, C, *g, st);
-  return launch_t<float, float>(A, B, C, *g, st);
+  return 0;
+}
+
+// one checked, non-empty product as its own launch
+int gemm_launch(const void* A, const void* B, void* C, const tm_gemm_args& g, hipStream_t st) {
+  if (g.ab_dtype == TM_BF16) {
+    if (g.c_dtype == TM_BF16) return launch_t<bf16, bf16>(A, B, C, g, st);
+    return launch_t<bf16, float>(A, B, C, g, st);
+  }
+  if (g.c_dtype == TM_BF16) return launch_t<float, bf16>(A, B, C, g, st);
+  return launch_t<float, float>(A, B, C, g, st);
+}
+
+}  // namespace
+
+extern "C" int tm_gemm(const void* A, const void* B, void* C, const tm_gemm_args* g, void* stream) {
+  PairState& ps = t_pair;
+  const bool hold = ps.open && ps.stream == stream;
+  bool empty;
+  const int rc = gemm_check(A, B, C, g, &empty);
+  if (rc != 0) {
+    if (hold) ps = PairState();   // an error inside a pair closes it: nothing stays held
+    return rc;
+  }
+  if (empty) return 0;
+  if (!hold) return gemm_launch(A, B, C, *g, (hipStream_t)stream);
+  if (ps.n == 2) {
+    ps = PairState();
+    tm_set_error("gemm: more than two calls between tm_gemm_pair_begin and tm_gemm_pair_end");
+    return 1;
+  }
+  ps.h[ps.n++] = HeldGemm{A, B, C, *g};
+  return 0;
+}
+
+extern "C" int tm_gemm_pair_begin(void* stream) {
+  PairState& ps = t_pair;
+  if (ps.open) {
+    ps = PairState();
+    tm_set_error("gemm_pair_begin: a pair is already open on this thread");
+    return 1;
+  }
+  ps.open = true;
+  ps.stream = stream;
+  ps.n = 0;
+  return 0;
+}
+
+extern "C" int tm_gemm_pair_end(void* stream) {
+  const PairState ps = t_pair;
+  if (!ps.open) return 0;   // closed by an error inside the pair (or never opened): nothing held
+  t_pair = PairState();     // whatever happens below, nothing stays held
+  TM_REQUIRE(ps.stream == stream, "gemm_pair_end: not the stream of tm_gemm_pair_begin");
+  hipStream_t st = (hipStream_t)stream;
+  if (ps.n == 2 && GEMM_SEL == GEMM_AUTO) {
+    if (pair_w_ok(ps.h[0].g) && pair_d_ok(ps.h[1].g)) return launch_pair(ps.h[0], ps.h[1], st);
+    if (pair_d_ok(ps.h[0].g) && pair_w_ok(ps.h[1].g)) return launch_pair(ps.h[1], ps.h[0], st);
+  }
+  for (int i = 0; i < ps.n; ++i) {   // not a pair this library fuses: separate launches in call order
+    const int rc = gemm_launch(ps.h[i].A, ps.h[i].B, ps.h[i].C, ps.h[i].g, st);
+    if (rc != 0) return rc;
+  }
+  return 0;
 }
 
 #ifdef TM_DIAG

@@ -363,6 +363,39 @@ def flush_reductions():
         q.flush()
 
 
+# The weight / data gradient GEMM pairs of the layer backward that leave as one launch in the bf16
+# step: "out" (layer 1's dW_out with dmerged) and "qkv" (layer 1's dW_qkv with dxn), each kept by its
+# own A/B against two launches.  "kv" (the class-row layer's k / v part of to_qkv's backward) can be
+# paired too but measured slower than its two launches and stays unpaired (DESIGN.md section 6,
+# "Paired backward GEMM launches"; profiles/r09b_ab_per_pair.txt).
+PAIR_SITES = ("out", "qkv")
+
+
+class gemm_pair:
+    """The two ``tm_gemm`` calls issued inside the block (a weight gradient and the data gradient
+    of the same dY: independent products) leave as ONE launch at exit (tm_gemm_pair_begin / _end,
+    gemm.hip's paired ring launch; bit-identical outputs).  ``on`` False, a probe target set (each
+    site's events must bracket its own kernel) or no bound reduce queue (the weight gradient's
+    slab sum would launch ahead of the held product) leaves the block's launches as they are."""
+
+    def __init__(self, on=True):
+        self.on = bool(on) and getattr(probe, "target", None) is None and getattr(_TLS, "queue", None) is not None
+
+    def __enter__(self):
+        if self.on:
+            _lib.call("tm_gemm_pair_begin", _stream())
+        return self
+
+    def __exit__(self, *exc):
+        if self.on:
+            try:
+                _lib.call("tm_gemm_pair_end", _stream())
+            except RuntimeError:
+                if exc[0] is None:
+                    raise           # else the block's own error is the one raised; the pair is closed
+        return False
+
+
 # ----------------------------------------------------------------------------- NystromAttention core
 def nystrom_core_forward(qkv, geo: Geometry, wconv, tdtype, dt_code, pool, cls_row=None):
     """App. A eq. 4-9 on q, k, v [3, B*h, n, 64] -> merged [B, n, h*64] (T) + saved state.
@@ -695,7 +728,8 @@ def translayer_forward(H, geo: Geometry, prm, tdtype, dt_code, pool, drop_p, see
     return Hout, saved
 
 
-def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_code, pool, dout=None, head=None):
+def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_code, pool, dout=None, head=None,
+                        pair_gemms=False):
     """dH [B*S, D] fp32 (gradient of the layer output) is turned IN PLACE into the
     gradient of the layer input.  Parameter gradients go to ``grads``.  ``dout``: the padded
     to_out-dropout gradient, already written by the producer of dH (tm_ppeg_bwd).  ``head``: the
@@ -703,6 +737,11 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
     by that launch from the CE head instead of read."""
     B, S, n, D, pad = geo.B, geo.S, geo.n, geo.D, geo.pad
     st = _stream()
+    # each weight gradient shares its data gradient's launch (bf16 step, 512-wide geometry only);
+    # pair_gemms: True (the pairs of PAIR_SITES), False, or the names to pair
+    on = dt_code == BF16 and (geo.dh, geo.nl) == (DH, NL)
+    names = PAIR_SITES if pair_gemms is True else (pair_gemms or ())
+    pair_out, pair_qkv, pair_kv = (on and k in names for k in ("out", "qkv", "kv"))
     if saved["cls_only"]:
         # dH is zero outside the class rows: dropout, dWo, dbo and dmerged on those rows only
         dmerged = pool(B * D, tdtype).view(B, D)
@@ -720,12 +759,13 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
             _lib.call("tm_dropout_bwd_pad", dt_code, _p(dH), B, S, n, pad, D, C.c_float(saved["drop_p"]),
                       C.c_uint64(saved["seed"]), _p(saved["seed_dev"]), _p(dout), st)
         # to_out: dWo = dout^T merged ; dbo = colsum(dout) ; dmerged = dout Wo
-        with defer_reductions(), probe("wgrad_out"):
-            weight_grad(dout, saved["merged"], grads["wo"], D, D, B * n, ldy=D, ldx=D, dtype=dt_code,
-                        work_pool=pool, bias_out=grads["bo"])
         dmerged = pool(B * n * D, tdtype).view(B, n, D)
-        with probe("dmerged_gemm"):
-            gemm(dout, prm["wo"], dmerged, B * n, D, D, lda=D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
+        with gemm_pair(pair_out):
+            with defer_reductions(), probe("wgrad_out"):
+                weight_grad(dout, saved["merged"], grads["wo"], D, D, B * n, ldy=D, ldx=D, dtype=dt_code,
+                            work_pool=pool, bias_out=grads["bo"])
+            with probe("dmerged_gemm"):
+                gemm(dout, prm["wo"], dmerged, B * n, D, D, lda=D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
     # bf16 class-row layer: q reaches the loss only through its landmark means and the class row, so
     # the q part of to_qkv's backward runs as two small products on tm_cls_q_rows' operands
     qrows_on = (CLS_Q_ROWS and saved["cls_only"] and dt_code == BF16 and saved["core"]["a2s"] is not None
@@ -738,11 +778,12 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
     rpb = _LN_BWD_RPB
     if qrows is None:
         # to_qkv: dWqkv = dqkv^T xn ; dxn = dqkv Wqkv
-        with defer_reductions(), probe("wgrad_qkv"):
-            weight_grad(dqkv, saved["xn"], grads["wqkv"], 3 * D, D, B * n, ldy=3 * D, ldx=D, dtype=dt_code,
-                        work_pool=pool)
-        with probe("dxn_gemm"):
-            gemm(dqkv, prm["wqkv"], dxn, B * n, D, 3 * D, lda=3 * D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
+        with gemm_pair(pair_qkv):
+            with defer_reductions(), probe("wgrad_qkv"):
+                weight_grad(dqkv, saved["xn"], grads["wqkv"], 3 * D, D, B * n, ldy=3 * D, ldx=D, dtype=dt_code,
+                            work_pool=pool)
+            with probe("dxn_gemm"):
+                gemm(dqkv, prm["wqkv"], dxn, B * n, D, 3 * D, lda=3 * D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
         # LayerNorm backward, accumulated into dH (residual branch already there)
         with defer_reductions():
             work = pool(_lib.query("tm_layernorm_bwd_workspace", B * S, D, rpb) // 4)
@@ -753,11 +794,12 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
         return
     # k / v parts: dW_kv = dqkv_kv^T xn, dxn = dqkv_kv W_kv (K = 2D instead of 3D)
     dkv = dqkv.view(B * n, 3 * D)[:, D:]
-    with defer_reductions(), probe("wgrad_qkv"):
-        weight_grad(dkv, saved["xn"], grads["wqkv"][D:], 2 * D, D, B * n, ldy=3 * D, ldx=D, dtype=dt_code,
-                    work_pool=pool)
-    with probe("dxn_gemm"):
-        gemm(dkv, prm["wqkv"][D:], dxn, B * n, D, 2 * D, lda=3 * D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
+    with gemm_pair(pair_kv):
+        with defer_reductions(), probe("wgrad_qkv"):
+            weight_grad(dkv, saved["xn"], grads["wqkv"][D:], 2 * D, D, B * n, ldy=3 * D, ldx=D, dtype=dt_code,
+                        work_pool=pool)
+        with probe("dxn_gemm"):
+            gemm(dkv, prm["wqkv"][D:], dxn, B * n, D, 2 * D, lda=3 * D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
     # q part: dWq = scale Aq^T Xs ; G = scale Aq Wq (its rows added to dxn by segment in the LN backward)
     Aq, Xs = qrows
     scale = DH ** -0.5
@@ -796,6 +838,11 @@ class TransMILEngine:
     code/models/MDMIL.py:73).
     ``cls_only``: layer 2's attention output / to_out forward and backward on the class rows only
     (the logits read nothing else of it; clsrow.hip).  False runs them dense (same results)."""
+
+    # the layer backward's weight / data gradient GEMM pairs as one launch each (bf16 mode only):
+    # True = the pairs of PAIR_SITES, False = every product its own launch (same results bit for
+    # bit), or a collection of names among "out", "qkv", "kv"
+    pair_gemms = True
 
     def __init__(self, dtype: torch.dtype = torch.bfloat16, fc1=None, head="_fc", cls_only=True):
         if dtype not in (torch.bfloat16, torch.float32):
@@ -1044,7 +1091,7 @@ class TransMILEngine:
                   "wqkv": g[pre + "attn.to_qkv.weight"], "wconv": g[pre + "attn.res_conv.weight"],
                   "norm_w": g[pre + "norm.weight"], "norm_b": g[pre + "norm.bias"]}
             translayer_backward(dH, Hin, saved, geo, prm[li], gl, self.tdtype, self.dt_code, pool, dout=dout1,
-                                head=head if li == 2 else None)
+                                head=head if li == 2 else None, pair_gemms=self.pair_gemms)
             if li == 2:
                 dH1 = pool(B * S * D).view(B * S, D)
                 work = pool(_lib.query("tm_ppeg_bwd_workspace", B, geo.G, D) // 4)
