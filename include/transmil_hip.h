@@ -407,6 +407,36 @@ int tm_attmil_bwd(const float* Z, const float* H, const float* w, const float* p
                   const float* Wc, const float* dlogits, int N, int L, int D, int C, float* work,
                   float* dZ, float* dH, float* dM, float* dw, float* db, float* dWc, float* dbc, void* stream);
 
+/* ---- Chowder scores, two-sided top-R and head (chowder.hip) -- code/models/Chowder.py:19-50 ----
+ * x [B, N, L] contiguous of dtype TM_F32 / TM_BF16 (all arithmetic fp32), w [L] / b [1] = the 1x1
+ * Conv1d f1, W1 [H1, 2R] / b1, W2 [H2, H1] / b2, W3 [C, H2] / b3 = the three Linear layers of f2.
+ * Limits: L a multiple of 8 and <= 4096, 1 <= R <= 32, N >= R, 1 <= B <= 65535, H1 / H2 / C in
+ * [1, 1024]; anything else returns non-zero with a tm_last_error() text and launches nothing.
+ * Forward (two launches): s[b,n] = x[b,n,:] . w + b, summed in an order that depends on L only (a
+ * row gives the same bits wherever it stands); scores (nullable) [B, N] receives s.
+ * vals [B, 2R] = (R smallest ascending, then R largest descending), the layout of
+ * torch.cat((topk(largest=False).values, topk.values)); idx [B, 2R] int32 the instance indices.  Among
+ * equal scores the lower index is selected first, in both selections.  With N < 2R an instance can
+ * stand in both selections; it then appears twice.  Non-finite scores are out of contract: the
+ * selection is then unspecified, but every idx is in [0, N) and nothing is read or written out of
+ * bounds.  hid [B, H1 + H2] = (h1 = W1 vals + b1, h2 = W2 h1 + b2), logits [B, C] = W3 h2 + b3.
+ * Backward (two launches and, with dx, one memset): from dlogits [B, C] the six head gradients,
+ * dw [L] = sum_b sum_j dvals[b,j] x[b, idx[b,j], :] and db [1] = sum dvals, every sum in the fixed
+ * order b, then j (no float atomics: bitwise repeatable).  dx (nullable) [B, N, L] fp32 is
+ * zero-filled and row idx[b,j] receives dvals[b,j] w, an instance selected twice the sum of both.
+ * An idx outside [0, N) is skipped.  work is sized by the queries (0 for a shape outside the limits). */
+long long tm_chowder_fwd_workspace(int B, int N, int L, int R);
+int tm_chowder_fwd(int dtype, const void* x, int B, int N, int L, const float* w, const float* b, int R,
+                   const float* W1, const float* b1, int H1, const float* W2, const float* b2, int H2,
+                   const float* W3, const float* b3, int C, void* work, float* scores, float* vals,
+                   int* idx, float* hid, float* logits, void* stream);
+long long tm_chowder_bwd_workspace(int B, int L, int R, int H1, int H2, int C);
+int tm_chowder_bwd(int dtype, const void* x, int B, int N, int L, const float* w, int R, const float* W1,
+                   int H1, const float* W2, int H2, const float* W3, int C, const float* vals,
+                   const int* idx, const float* hid, const float* dlogits, void* work, float* dw,
+                   float* db, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
+                   float* dx, void* stream);
+
 /* ---- feature-bag sampling (bags.hip) -- code/datasets/feature_dataloader.py:335-431 ----
  * dst[r] = src[i0[r]] (i1 NULL or i1[r] < 0), (src[i0[r]] * wa[r]) + (src[i1[r]] * wb[r]) (mixup),
  * or 0 (i0[r] < 0); src [*, F] and dst [nrows, F] of dtype TM_F32 / TM_BF16, i0/i1 int64 row

@@ -147,6 +147,10 @@ _SIGS = {
     "tm_attmil_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
     "tm_attmil_bwd_workspace": (L, [I, I, I]),
     "tm_attmil_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]),
+    "tm_chowder_fwd_workspace": (L, [I, I, I, I]),
+    "tm_chowder_fwd": (I, [I, P, I, I, I, P, P, I, P, P, I, P, P, I, P, P, I, P, P, P, P, P, P, P]),
+    "tm_chowder_bwd_workspace": (L, [I, I, I, I, I, I]),
+    "tm_chowder_bwd": (I, [I, P, I, I, I, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
     "tm_put_cls": (I, [P, I, I, I, P, P]),
     "tm_step_prepare": (I, [I, C.POINTER(CastTable), P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, P]),
     "tm_reduce_queue_create": (P, []),

@@ -94,11 +94,30 @@ def build_model(cfg, device="cuda"):
     name = cfg.Model.name
     if not hasattr(models, name):
         raise ValueError(f"Model.name {name!r} is not on the MI355X path "
-                         "(TransMIL, MDMIL, CTMIL, TransformerMIL, AttMIL)")
+                         "(TransMIL, MDMIL, CTMIL, TransformerMIL, AttMIL, Chowder)")
     klass = getattr(models, name)
     n_classes = int(cfg.Model.n_classes)
     if name == "MDMIL":
         model = klass(n_classes)
+    elif name == "Chowder":
+        # instancialize's rule (model_interface.py:1278-1293): only the constructor arguments that
+        # cfg.Model names are passed, and in_features / out_features are not among Chowder's
+        kw = {k: int(cfg.Model[k]) for k in ("features", "r") if cfg.Model.get(k) is not None}
+        model = klass(n_classes, **kw)
+        # Where the config fixes the bags' width (Data.feature_extractor as code/train.py:392-397 reads
+        # it, or an on-GPU tile encoder), it must be Chowder's `features`: nothing maps one width to
+        # the other in this model, and the reference's Conv1d(features, 1, 1) cannot take such bags either
+        fe = (cfg.Data or {}).get("feature_extractor")
+        backbone = _image_backbone(cfg)
+        source, width = None, None
+        if fe in _FEATURE_WIDTH:
+            source, width = f"Data.feature_extractor {fe}", _FEATURE_WIDTH[fe]
+        elif backbone is not None:
+            source = f"backbone {backbone}"
+            width = {"retccl": _FEATURE_WIDTH["retccl"], "resnet18": _RESNET18_WIDTH, "simple": _SIMPLE_WIDTH}[backbone]
+        if width is not None and width != model.L:
+            raise ValueError(f"Model.name 'Chowder' with features = {model.L} is not on the MI355X path for "
+                             f"{source}, whose bags are {width} wide: set Model.features: {width}")
     else:
         model = klass(n_classes, in_features_of(cfg), int(cfg.Model.out_features or 512))
     model = model.to(device)

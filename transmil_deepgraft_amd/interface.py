@@ -871,7 +871,12 @@ class TransMILTask(nn.Module):
         self._last_loss = None
 
     def forward(self, x):
-        return self.model(x)
+        out = self.model(x)
+        if isinstance(out, tuple):          # Chowder returns (logits, None), [B, 1, C] for B > 1
+            out = out[0]
+        if out.dim() == 3 and out.shape[1] == 1:
+            out = out.view(out.shape[0], out.shape[2])
+        return out
 
     def step(self, bags):
         logits = self(_model_input(bags))
@@ -1123,7 +1128,8 @@ class GraphedOptimizationStep:
 
     One bag shape per instance (the reference's loaders sample bags to a fixed size); a batch of
     another shape raises.  Returns the training_step loss tensor of the replayed graph (a static
-    buffer: it is overwritten by the next call of the same phase).
+    buffer: it is overwritten by the next call of the same phase); the eager window's calls return
+    their loss detached (the step has run; see ``__call__``).
 
     Learning rate / weight decay: with ``FusedRAdamLookahead`` the replayed update reads them from
     a device array refreshed from the param groups before every replayed optimizer step, so an LR
@@ -1215,7 +1221,12 @@ class GraphedOptimizationStep:
         if self.graphs is None:
             if self.shape is None:
                 self.shape = (tuple(bags.shape), tuple(label.shape))
-            loss = task.optimization_step(batch, self.opt, allreduce=self.allreduce)
+            # The eager steps' losses are returned detached, so that their autograd graphs are gone
+            # before the capture.  While such a graph lives, the parameters keep its AccumulateGrad
+            # nodes, which are bound to the stream the eager step ran on; a captured backward that
+            # reaches them (a model whose gradients autograd accumulates, unlike TransMIL's fused
+            # backward) would make that stream wait on the capturing one.
+            loss = task.optimization_step(batch, self.opt, allreduce=self.allreduce).detach()
             if task._micro % self.k == 0:        # the eager window is complete: capture
                 self._capture(bags, label)
             return loss

@@ -6,3 +6,4 @@ from .MDMIL import MDMIL  # noqa: F401
 from .CTMIL import CTMIL  # noqa: F401
 from .TransformerMIL import TransformerMIL  # noqa: F401
 from .AttMIL import AttMIL  # noqa: F401
+from .Chowder import Chowder  # noqa: F401
