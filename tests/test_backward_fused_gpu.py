@@ -585,3 +585,39 @@ def test_splitk_reduce_bf16_is_the_index_order_fp32_sum(splits, count, accumulat
         ulps = ((outs[0] - want).abs() / torch.maximum(_ulp_f32(want), _ulp_f32(outs[0]))).max().item()
         _report(f"splitk_reduce_bf16 alpha 0.5 [fp32 ulp] {splits, count, accumulate}", ulps)
         assert ulps <= 1.0
+
+
+# ============================================================================= g. tm_splitk_reduce (fp32 slabs)
+@pytest.mark.parametrize("alpha", [1.0, 0.5])
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("count", [4096, 4099])
+@pytest.mark.parametrize("splits", [1, 5, 16, 33])
+def test_splitk_reduce_f32_is_the_index_order_fp32_sum(splits, count, accumulate, alpha):
+    """out (= / +=) alpha * sum_z slab[z] over fp32 slabs, bit for bit the fp32 sum in the order
+    kernel_refs.slab_sum_f32 restates (index order; 33 splits exceed one unrolled group of loads and
+    give every output two lanes, reduce_par); count = 4099 takes the element-by-element form, 4096 the
+    16-B one of the flush launch.  alpha = 0.5 scales exactly, so alpha * s + out rounds once whether
+    or not it is one fma: bitwise there too.  The immediate launch and a caller-owned queue flushed
+    afterwards give the same bits."""
+    L = _lib()
+    _p, _stream = _eng()
+    g = torch.Generator(device="cpu").manual_seed(splits * 11 + count)
+    slab = torch.randn(splits, count, generator=g)
+    base = torch.randn(count, generator=g)
+    s = R.slab_sum_f32(slab, R.reduce_par(splits, count, bf16=False)) * alpha
+    want = s + base if accumulate else s
+    slabd = slab.to(DEV)
+    for queued in (False, True):
+        out = base.clone().to(DEV) if accumulate else torch.full((count,), NAN, device=DEV)
+        if queued:
+            with _Queue() as q:
+                L.call("tm_splitk_reduce", _p(slabd), _p(out), splits, count, C.c_float(alpha), accumulate, q.h,
+                       _stream())
+                assert q.pending() == 1
+                q.flush()
+                torch.cuda.synchronize()
+        else:
+            L.call("tm_splitk_reduce", _p(slabd), _p(out), splits, count, C.c_float(alpha), accumulate, None,
+                   _stream())
+            torch.cuda.synchronize()
+        assert torch.equal(out.cpu(), want), ("queued" if queued else "immediate")

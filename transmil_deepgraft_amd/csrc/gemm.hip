@@ -877,7 +877,7 @@ __global__ __launch_bounds__(640) void gemm_ring160_kernel(const bf16* __restric
   const int wm = wave >> 1, wn = wave & 1;   // 5 (M) x 2 (N) waves of 32 x 64
   int m0, n0;
   tile160_of_block(m0, n0);
-  const int nk = g.K / 64;                   // host guarantees 64 | K
+  const int nk = g.K / 64;                   // host guarantees 64 | K and K >= 64 (ring160_ok)
 
   f32x16 acc[2];
   acc[0] = (f32x16){};
@@ -909,7 +909,7 @@ __global__ __launch_bounds__(640) void gemm_ring160_kernel(const bf16* __restric
     }
     if (wave < 8) glds_tile<B_KN>(st + R160_A, B, g.ldb, n0, g.N, k0, wave, lane);
   };
-  issue(0);
+  issue(0);   // nk >= 1 (ring160_ok): tile 0 exists
   for (int kt = 0; kt < nk; ++kt) {
     // this wave's pieces of tile kt landed (tile kt + 1 not yet issued: wait for all)
     wait_vm<0>();
@@ -1188,8 +1188,13 @@ inline bool ring_ok(const tm_gemm_args& g) {
   return true;
 }
 
-// 160-row tiles: k-contiguous A, no split
+// 160-row tiles: k-contiguous A, no split, at least one k-tile.  The kernel issues its first stage
+// before it looks at the k-tile count (with K = 0 it would DMA-read 64 columns of A and B that do not
+// exist), so K = 0 (bias / addend only) goes to the 128-row ring, which issues under `t < nk`.  The
+// same test inside the kernel moved its first loads behind a branch and cost the step 0.1 % in every
+// placement tried ("tm_gemm: which shapes reach which kernel").
 inline bool ring160_ok(const tm_gemm_args& g) {
+  if (g.K < 64) return false;
   if (g.a_trans || g.splits != 1 || g.K % 64 != 0 || g.M < BM160 || g.mode == TM_EPI_SPLITK) return false;
   if (g.b_kn && (g.N % 8 != 0 || g.N < 8)) return false;
   return true;
