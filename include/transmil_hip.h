@@ -437,6 +437,46 @@ int tm_chowder_bwd(int dtype, const void* x, int B, int N, int L, const float* w
                    float* db, float* dW1, float* db1, float* dW2, float* db2, float* dW3, float* db3,
                    float* dx, void* stream);
 
+/* ---- CLAM_MB gated attention pooling, instance selection and instance loss (clam.hip) --
+ * code/models/model_clam.py:195-268 ----
+ * fp32.  Z [N, 2D] = h [Wa;Wb]^T + [ba;bb] and h [N, L] = ReLU(x W1^T + b1) come from the caller's
+ * GEMMs; Wc [K, D] / bc [K] = attention_c, Wcls [K, L] / bcls [K] = the K Linear(L, 1) bag classifiers
+ * stacked, Wic [K, 2, L] / bic [K, 2] = the K instance classifiers stacked.  Limits: L == 512, D a
+ * multiple of 4 and <= 512, 1 <= K <= 8, 1 <= k_sample <= 32, N >= k_sample; anything else returns
+ * non-zero with a tm_last_error() text and launches nothing.
+ * tm_clam_fwd (two launches): A_raw [K, N] the scores a[c,i] = Wc[c] . (tanh(Z[i,:D]) sigmoid(Z[i,D:]))
+ * + bc[c]; stats [K, 2] = {max_i a[c,i], sum_i exp(a[c,i] - max)}; M [K, L] = softmax_N(a) h;
+ * logits [K] = Wcls[c] . M[c] + bcls[c].  label (nullable, a DEVICE int64, read by the kernel only)
+ * switches the instance evaluation on: class y = label takes the k_sample largest scores of a[y,:]
+ * in descending order (targets 1), then the k_sample smallest in ascending order (targets 0); with
+ * subtyping every other class takes its k_sample largest (targets 0); among equal scores the lower
+ * index first.  idx / preds / targets [K, 2 k_sample] int32 (-1 in the slots of a class that is not
+ * evaluated and in the second half of an out-of-class row), dil [K, 2 k_sample, 2] =
+ * d inst_loss / d il, inst_loss [1] = sum over the evaluated classes of the mean cross entropy of
+ * il = h[idx] Wic[c]^T + bic[c] (divided by K with subtyping).  Non-finite scores are out of contract:
+ * every idx still lies in [0, N).  tm_clam_scores: A_raw alone (one launch).
+ * tm_clam_bwd (three launches): from dlogits [K] and dloss [1] (both nullable: zero) writes dZ [N, 2D],
+ * dH [N, L] = sum_c p dM[c] plus the instance classifiers' contributions to the selected rows (the
+ * caller's GEMM then adds dZ [Wa;Wb]), dWc [K, D], dbc [K], dWcls [K, L], dbcls [K] and, with idx
+ * (nullable: no instance evaluation), dWic [K, 2, L] and dbic [K, 2].  Every sum has one fixed order
+ * (no float atomics): bitwise repeatable.  tm_clam_relu_bwd: dh = h > 0 ? dh : 0 in place (count a
+ * multiple of 4).  work is sized by the queries (0 for a shape outside the limits). */
+long long tm_clam_fwd_workspace(int N, int K);
+int tm_clam_scores(const float* Z, int N, int D, int K, const float* Wc, const float* bc, float* A_raw,
+                   void* stream);
+int tm_clam_fwd(const float* Z, const float* H, int N, int L, int D, int K, const float* Wc,
+                const float* bc, const float* Wcls, const float* bcls, const float* Wic, const float* bic,
+                const long long* label, int k_sample, int subtyping, float* work, float* A_raw,
+                float* stats, float* M, float* logits, float* inst_loss, int* idx, int* preds,
+                int* targets, float* dil, void* stream);
+long long tm_clam_bwd_workspace(int N, int D, int K, int k_sample);
+int tm_clam_bwd(const float* Z, const float* H, const float* A_raw, const float* stats, const float* M,
+                int N, int L, int D, int K, const float* Wc, const float* Wcls, const float* Wic,
+                const int* idx, const float* dil, int k_sample, const float* dlogits, const float* dloss,
+                float* work, float* dZ, float* dH, float* dWc, float* dbc, float* dWcls, float* dbcls,
+                float* dWic, float* dbic, void* stream);
+int tm_clam_relu_bwd(float* dh, const float* h, long long count, void* stream);
+
 /* ---- feature-bag sampling (bags.hip) -- code/datasets/feature_dataloader.py:335-431 ----
  * dst[r] = src[i0[r]] (i1 NULL or i1[r] < 0), (src[i0[r]] * wa[r]) + (src[i1[r]] * wb[r]) (mixup),
  * or 0 (i0[r] < 0); src [*, F] and dst [nrows, F] of dtype TM_F32 / TM_BF16, i0/i1 int64 row

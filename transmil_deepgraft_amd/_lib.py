@@ -151,6 +151,12 @@ _SIGS = {
     "tm_chowder_fwd": (I, [I, P, I, I, I, P, P, I, P, P, I, P, P, I, P, P, I, P, P, P, P, P, P, P]),
     "tm_chowder_bwd_workspace": (L, [I, I, I, I, I, I]),
     "tm_chowder_bwd": (I, [I, P, I, I, I, P, I, P, I, P, I, P, I, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "tm_clam_fwd_workspace": (L, [I, I]),
+    "tm_clam_scores": (I, [P, I, I, I, P, P, P, P]),
+    "tm_clam_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P]),
+    "tm_clam_bwd_workspace": (L, [I, I, I, I]),
+    "tm_clam_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
+    "tm_clam_relu_bwd": (I, [P, P, L, P]),
     "tm_put_cls": (I, [P, I, I, I, P, P]),
     "tm_step_prepare": (I, [I, C.POINTER(CastTable), P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, P]),
     "tm_reduce_queue_create": (P, []),

@@ -94,7 +94,7 @@ def build_model(cfg, device="cuda"):
     name = cfg.Model.name
     if not hasattr(models, name):
         raise ValueError(f"Model.name {name!r} is not on the MI355X path "
-                         "(TransMIL, MDMIL, CTMIL, TransformerMIL, AttMIL, Chowder)")
+                         "(TransMIL, MDMIL, CTMIL, TransformerMIL, AttMIL, Chowder, CLAM_MB)")
     klass = getattr(models, name)
     n_classes = int(cfg.Model.n_classes)
     if name == "MDMIL":
@@ -118,6 +118,25 @@ def build_model(cfg, device="cuda"):
         if width is not None and width != model.L:
             raise ValueError(f"Model.name 'Chowder' with features = {model.L} is not on the MI355X path for "
                              f"{source}, whose bags are {width} wide: set Model.features: {width}")
+    elif name == "CLAM_MB":
+        # instancialize's rule again: only the constructor arguments that cfg.Model names are passed
+        # (n_classes among them); in_features / out_features are not CLAM_MB's
+        kinds = {"gate": bool, "size_arg": str, "dropout": bool, "k_sample": int, "subtyping": bool}
+        kw = {k: kind(cfg.Model[k]) for k, kind in kinds.items() if cfg.Model.get(k) is not None}
+        model = klass(n_classes=n_classes, **kw)
+        # CLAM_MB's first layer is Linear(1024, 512) for both sizes: where the config fixes the bags'
+        # width, it must be 1024 (the reference's size_dict cannot take other bags either)
+        fe = (cfg.Data or {}).get("feature_extractor")
+        backbone = _image_backbone(cfg)
+        source, width = None, None
+        if fe in _FEATURE_WIDTH:
+            source, width = f"Data.feature_extractor {fe}", _FEATURE_WIDTH[fe]
+        elif backbone is not None:
+            source = f"backbone {backbone}"
+            width = {"retccl": _FEATURE_WIDTH["retccl"], "resnet18": _RESNET18_WIDTH, "simple": _SIMPLE_WIDTH}[backbone]
+        if width is not None and width != 1024:
+            raise ValueError(f"Model.name 'CLAM_MB' (bags of 1024 features) is not on the MI355X path for "
+                             f"{source}, whose bags are {width} wide")
     else:
         model = klass(n_classes, in_features_of(cfg), int(cfg.Model.out_features or 512))
     model = model.to(device)

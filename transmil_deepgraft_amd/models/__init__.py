@@ -7,3 +7,4 @@ from .CTMIL import CTMIL  # noqa: F401
 from .TransformerMIL import TransformerMIL  # noqa: F401
 from .AttMIL import AttMIL  # noqa: F401
 from .Chowder import Chowder  # noqa: F401
+from .CLAM import CLAM_MB  # noqa: F401
