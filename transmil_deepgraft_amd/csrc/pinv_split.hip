@@ -21,6 +21,12 @@
 // (both bank-conflict free; the swizzle is applied to the DMA source address).  The epilogue
 // stages the fp32 tile through LDS and writes whole 16-B row pieces: scale, diagonal, up to two
 // addend matrices, and up to four outputs (split, fp32, and two split side outputs).
+// Entry sequence of a workgroup (grid (nbh, 16, njobs): head, tile, job, no division): four wide
+// scalar loads bring the job descriptor (SJob, three 64-B lines) and the launch-wide scalars into
+// SGPRs; the lane's own address arithmetic runs under them; one wait; the producers issue chunk 0,
+// then (waves 4-7, which also own an epilogue piece) the plain loads of the epilogue addends, then
+// chunk 1.  Nothing after the wait loads from the kernel argument again: the walk and the epilogue's
+// store sequence run on SGPRs ("The pseudo-inverse chain", has the measured table).
 //
 // Forward schedule (P_k = X Z_k, carried by its own recurrence, as in pinv.hip), per layer:
 //   L1:  S = X X^T                       + |X| row / column sums, per-head maxima
@@ -61,7 +67,8 @@ struct SOp {
 
 enum { KIND_PRODUCT = 0, KIND_ABSSUMS = 1 };
 
-struct SJob {
+// One job's descriptor: three 64-B lines, read once at kernel entry (pinv_stage_kernel)
+struct alignas(64) SJob {
   SOp a[2], b[2];
   int nterms, kind;
   float alpha, diag;       // s = alpha * invc^alpha_cpow * sum;  v = s + diag*I + e1s*E1' + e2s*E2
@@ -73,6 +80,7 @@ struct SJob {
   bf16* c2; float c2_alpha, c2_diag, c2_e1; // optional split: c2_alpha*s + c2_diag*I + c2_e1*E1'
   bf16* c3; float c3_e1; int pad1;          // optional split: c3_e1 * E1'
 };
+static_assert(sizeof(SJob) == 192, "SJob: three 64-B lines");
 // The DOT stage-kernel instantiation (the backward's last level only) reads its job's e2 as
 // `dotx` (fp32, head-major like the output; that job has no E2 addend) and cf as `dot_part`: the
 // workgroup's partial of sum_ij v[i][j] dotx[j][i] at dot_part[head * 16 + tile] -- the c
@@ -88,7 +96,7 @@ struct SLaunch {
   const float* X;           // fp32 X (abs-sum jobs)
   float* sums;              // [2][nbh][256] row / column sums (abs-sum jobs)
   float* maxima_out;        // [2][nbh] (abs-sum jobs)
-  A3Combine a3;             // a3.w non-null: the row blockIdx.y == njobs runs the A3 forward's partial
+  A3Combine a3;             // a3.w non-null: the row blockIdx.z == njobs runs the A3 forward's partial
                             // combine (a3_combine.h) on the CUs the chain's tiles leave idle
 #ifdef TM_DIAG
   unsigned long long* stamps;  // per-wave s_memtime stamps of the product workgroups, or null
@@ -113,6 +121,13 @@ TM_DEV unsigned long long rstamp() {
   asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
   return t;
 }
+
+typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+typedef unsigned u32x8_t __attribute__((ext_vector_type(8)));
+typedef unsigned u32x16_t __attribute__((ext_vector_type(16)));
+// the same pointer, known to the compiler as global memory
+template <class T> TM_DEV T* as_global(T* p) { return (T*)(__attribute__((address_space(1))) T*)p; }
 
 TM_DEV float powc(float c, int p) { return p == 0 ? 1.f : (p == 1 ? c : c * c); }
 
@@ -222,7 +237,6 @@ TM_DEV void load_split8(const bf16* hi, long long plane, size_t off, float* v) {
 }
 // 16-B store; wt: write-through (buffer_store sc1: the line goes out now and leaves this XCD's L2,
 // so the launch-end L2 write-back has nothing of it to write)
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 TM_DEV void st16(void* base, size_t off_bytes, f32x4 v, bool wt) {
   if (wt)
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), tm_rsrc(base, 0x7FFFFFF0u),
@@ -278,6 +292,39 @@ TM_DEV void abssums(const SLaunch& L, int head, int which, float* red) {
   if (t == 0) L.maxima_out[which * L.nbh + head] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// What a wave's addresses take from its thread index alone, worked out while the descriptor's
+// scalar loads are in flight (pinv_stage_kernel):
+//   producer wave p = wv - 4: pre[kr * PPW + i] = the source offset of piece i in a "kc" (kr = 0) or
+//     "kr" (kr = 1) image: row * 256 + 8 * (slot ^ swizzle(row));
+//   consumer wave: pre[0..3] / pre[4..7] = the A / B "kc" fragment addresses of k-steps 0..3,
+//     pre[8] / pre[9] = the A / B "kr" fragment address.
+constexpr int PPW = 32 / NPROD;   // 8-row pieces of one plane chunk per producer wave
+constexpr int NPRE = 10;
+static_assert(2 * PPW <= NPRE, "pre[] holds a producer's offsets");
+TM_DEV void lane_addresses(int wv, int lane, const char* smem, unsigned (&pre)[NPRE]) {
+  if (wv >= 4) {
+    const int rb = ((wv - 4) % (NPROD / 4)) * PPW * 8;
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) {
+      const int row = rb + i * 8 + (lane >> 3), pos = lane & 7;
+      pre[i] = row * NL + 8 * (pos ^ ((row >> 1) & 7));
+      pre[PPW + i] = row * NL + 8 * (pos ^ (((row >> 1) & 1) << 2));
+    }
+#pragma unroll
+    for (int i = 2 * PPW; i < NPRE; ++i) pre[i] = 0;
+  } else {
+    const int wm = wv >> 1, wn = wv & 1;
+    const unsigned lbase = lds_off(smem);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      pre[s] = lbase + kc_addr(wm * 32, s, lane);
+      pre[4 + s] = lbase + kc_addr(wn * 32, s, lane);
+    }
+    pre[8] = lbase + kr_addr(wm * 32, lane);
+    pre[9] = lbase + kr_addr(wn * 32, lane);
+  }
+}
+
 // Roles: waves 0-3 are consumers (one 32x32 subtile each, the whole K: LDS reads + MFMAs +
 // epilogue), waves 4-7 producers (wave 4+p issues plane p of every chunk by LDS-DMA: 0 A hi,
 // 1 A lo, 2 B hi, 3 B lo).  One s_barrier per chunk: a chunk is read after the barrier that
@@ -285,25 +332,29 @@ TM_DEV void abssums(const SLaunch& L, int head, int which, float* red) {
 // follows the consumers' last read of it.
 template <bool DOT = false>
 TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* maxima, int head, int tile,
-                       char* smem, unsigned long long* stamp_out, bool dj = false) {
+                       char* smem, const unsigned (&pre)[NPRE], unsigned long long* stamp_out, unsigned long long t0,
+                       unsigned long long t1, bool dj = false) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m0 = (tile >> 2) * 64, n0 = (tile & 3) * 64;
   const size_t hoff = (size_t)head * MAT;
   const int nch = J.nterms * 4;
   const bool st_on = SPLIT_STAMPS;
-  unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (st_on) { ts[0] = rstamp(); ts[1] = stamp(); }
+  unsigned long long ts[8] = {t0, t1, 0, 0, 0, 0, 0, 0};
 
-  // epilogue operands first (plain loads, issued before any DMA: every later counted wait covers
-  // them): this thread's 8-element row piece (row tid/8, cols 8 (tid&7)) of E1 / E2, raw 16-B words
+  // epilogue operands (plain loads): this thread's 8-element row piece (row tid/8, cols 8 (tid&7))
+  // of E1 / E2, raw 16-B words.  Waves 0-7 own the 512 pieces (a wave-uniform test: the waves that
+  // own none skip the loads by a scalar branch).  The consumers load them first; a producer that
+  // owns a piece loads them between its chunk 0 and chunk 1 (load_addends' call below).
   const int lr = tid >> 3, lc = (tid & 7) * 8;
   const size_t eoff = hoff + (size_t)(m0 + lr) * NL + n0 + lc;
   const void* e1p = J.e1;
   const void* e2p = J.e2;
   const int e1f = J.e1_f32, e2f = J.e2_f32;
   f32x4 e1raw[2], e2raw[2];
-  auto ld4 = [&](const f32x4* a) { return *a; };
+  typedef const __attribute__((address_space(1))) f32x4 gf32x4;
+  typedef const __attribute__((address_space(1))) float gfloat;
+  auto ld4 = [&](const f32x4* a) { return *(gf32x4*)a; };
   auto eload = [&](const void* e, int f32, f32x4 (&r)[2]) {
     if (f32) {
       const float* q = (const float*)e;
@@ -313,41 +364,40 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
       r[0] = ld4((const f32x4*)(q + eoff)); r[1] = ld4((const f32x4*)(q + plane + eoff));
     }
   };
-  const bool epi = tid < 512;  // the 512 threads that each own one 8-element piece of the 64x64 tile
-  if (e1p && epi) eload(e1p, e1f, e1raw);
+  const bool epi = wv < 8;  // the 512 threads that each own one 8-element piece of the 64x64 tile
   const bool dotj = DOT && dj;   // this job carries the c-gradient dot in e2 / cf (job_dotx)
-  if (!dotj && e2p && epi) eload(e2p, e2f, e2raw);
   // the transposed dotx piece of this thread's 8 outputs: dotx[col + e][row] (DOT: a separate
   // instantiation for the one launch that carries it, so the other levels keep their registers)
   float dxv[8];
-  if (dotj && epi) {
-    const float* dotx = job_dotx(J);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) dxv[e] = dotx[hoff + (size_t)(n0 + lc + e) * NL + m0 + lr];
-  }
-  // per-head maxima for 1/c: one raw vector load per lane now, reduced in the epilogue
+  // per-head maxima for 1/c: one raw vector load per lane, reduced in the epilogue
   const bool need_c = J.alpha_cpow || J.e1_cpow;
   float mcv = -INFINITY, mrv = -INFINITY;
-  if (need_c && nbh <= 64 && lane < nbh) { mcv = maxima[lane]; mrv = maxima[nbh + lane]; }
+  asm volatile("" : "+v"(mcv), "+v"(mrv));   // set here: hipcc drains the DMAs (vmcnt(0)) in front of a
+                                             // v_mov it sinks behind the first global_load_lds
+  auto load_addends = [&]() {
+    if (e1p) eload(e1p, e1f, e1raw);
+    if (!dotj && e2p) eload(e2p, e2f, e2raw);
+    if (dotj) {
+      const float* dotx = job_dotx(J);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) dxv[e] = *(gfloat*)(dotx + hoff + (size_t)(n0 + lc + e) * NL + m0 + lr);
+    }
+    if (need_c && nbh <= 64 && lane < nbh) { mcv = *(gfloat*)(maxima + lane); mrv = *(gfloat*)(maxima + nbh + lane); }
+  };
   float* ep = (float*)(smem + STAGE_LDS);  // [64][EROW] fp32 tile for the epilogue
 
   if (wv >= 4) {  // ------------------------------------------------------------ producer
     // producer p = wv - 4 (0..NPROD-1) stages image rows of plane p / (NPROD/4) (0 A hi, 1 A lo,
     // 2 B hi, 3 B lo): PPW pieces of 8 rows each, starting at row 8 * PPW * (p % (NPROD/4))
-    constexpr int PPW = 32 / NPROD;
     const int p = wv - 4, pl = p / (NPROD / 4), rb = (p % (NPROD / 4)) * PPW * 8;
     const SOp op0 = pl < 2 ? J.a[0] : J.b[0];
     const SOp op1 = pl < 2 ? J.a[1] : J.b[1];
     const int o0w = pl < 2 ? m0 : n0;
     const bf16* const pb0 = op0.p + hoff + ((pl & 1) ? plane : 0);
     const bf16* const pb1 = op1.p + hoff + ((pl & 1) ? plane : 0);
-    unsigned loff[2][PPW];  // [kr][piece]: row * 256 + 8 * (slot ^ swizzle(row))
+    unsigned loff[2][PPW];  // [kr][piece]: row * 256 + 8 * (slot ^ swizzle(row)) (lane_addresses)
 #pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-      const int row = rb + i * 8 + (lane >> 3), pos = lane & 7;
-      loff[0][i] = row * NL + 8 * (pos ^ ((row >> 1) & 7));
-      loff[1][i] = row * NL + 8 * (pos ^ (((row >> 1) & 1) << 2));
-    }
+    for (int i = 0; i < PPW; ++i) { loff[0][i] = pre[i]; loff[1][i] = pre[PPW + i]; }
     auto issue = [&](int c) {
       char* img = smem + (c % NSLOT) * SLOT + pl * PC + rb * 128;
       const int t = c >> 2, k0 = (c & 3) * 64;
@@ -358,7 +408,14 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
         __builtin_amdgcn_global_load_lds((glb_t*)(base + (kr ? loff[1][i] : loff[0][i])), (lds_t*)(img + i * 1024),
                                          16, 0, 0);
     };
+    // Chunk 0 goes out first.  The addend loads of the producers that own an epilogue piece sit
+    // between chunk 0 and chunk 1: the first counted wait below leaves exactly chunk 1's PPW DMAs
+    // outstanding, so it retires chunk 0 wherever the compiler places those plain loads (ahead of
+    // chunk 0, between the chunks or behind chunk 1), and every later wait is behind them.
     issue(0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (epi) load_addends();
+    __builtin_amdgcn_sched_barrier(0);
     issue(1);  // nch >= 4
     for (int c = 0; c < nch; ++c) {
       if (c + 1 < nch) wait_vm<PPW>(); else wait_vm<0>();
@@ -367,16 +424,13 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
       if (c + 2 < nch) issue(c + 2);
     }
   } else {  // ---------------------------------------------------------------- consumer
+    load_addends();
     const int wm = wv >> 1, wn = wv & 1;
     const int code0 = J.a[0].kr | (J.b[0].kr << 1), code1 = J.a[1].kr | (J.b[1].kr << 1);
-    const unsigned lbase = lds_off(smem);
     unsigned akc[4], bkc[4];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      akc[s] = lbase + kc_addr(wm * 32, s, lane);
-      bkc[s] = lbase + kc_addr(wn * 32, s, lane);
-    }
-    const unsigned akr = lbase + kr_addr(wm * 32, lane), bkr = lbase + kr_addr(wn * 32, lane);
+    for (int s = 0; s < 4; ++s) { akc[s] = pre[s]; bkc[s] = pre[4 + s]; }
+    const unsigned akr = pre[8], bkr = pre[9];
     f32x16 acc = (f32x16){};
     if (st_on) ts[2] = stamp();
     for (int c = 0; c < nch; ++c) {
@@ -465,7 +519,7 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
       if (lane == 0) dred[wv] = d;
       __syncthreads();   // every wave of the workgroup (the non-epilogue ones at their return)
       if (tid == 0)
-        job_dot_part(J)[(size_t)head * 16 + tile] =
+        *(__attribute__((address_space(1))) float*)(job_dot_part(J) + (size_t)head * 16 + tile) =
             ((dred[0] + dred[1]) + (dred[2] + dred[3])) + ((dred[4] + dred[5]) + (dred[6] + dred[7]));
     }
   }
@@ -480,18 +534,71 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
   }
 }
 
-// One launch = up to three independent jobs over all heads.  Grid: (16 * nbh, njobs);
-// blockIdx.y is the job.
+// One launch = up to three independent jobs over all heads.  Grid: (nbh, 16, njobs): blockIdx.x is
+// the head, blockIdx.y the 64x64 tile, blockIdx.z the job (the same linear workgroup order as a
+// (16 * nbh, njobs) grid, without the division by nbh between the descriptor's arrival and the
+// first DMA).
 // AUX: the launch carries the A3 combine row (only the forward's last level; a separate
 // instantiation, so the other levels' code is not touched by the combine's registers)
 template <bool AUX, bool DOT = false>
 __global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  if (AUX && blockIdx.y == (unsigned)L.njobs) {
+  unsigned long long t0 = 0, t1 = 0;
+#ifdef TM_DIAG
+  t0 = rstamp(); t1 = stamp();   // ahead of the descriptor loads: `setup` counts them
+#endif
+  // The workgroup's job (three 64-B lines) and the launch-wide scalars, read once by four wide scalar
+  // loads issued here as one statement; the second statement, after the lane's own address
+  // arithmetic (which needs no field and runs while the loads are in flight), holds the one wait.
+  // hipcc does not count these loads: nothing may touch `raw` / `rs` between the two statements (they
+  // are only operands of the second; check the listing when the compiler changes: scripts/isa_diff.py),
+  // and everything after it takes the fields from its outputs, so no
+  // later use can turn back into a load from the kernel argument (the producer loop, the consumer
+  // loop and the epilogue run on SGPRs).  (The AUX row's blockIdx.z is njobs: clamped, its copy is
+  // not used.)
+  static_assert(offsetof(SLaunch, j) == 0 && offsetof(SLaunch, njobs) == MAXJ * sizeof(SJob), "SLaunch layout");
+  static_assert(offsetof(SLaunch, nbh) == offsetof(SLaunch, njobs) + 4 && offsetof(SLaunch, plane) == offsetof(SLaunch, njobs) + 8 &&
+                offsetof(SLaunch, maxima) == offsetof(SLaunch, njobs) + 16, "SLaunch scalars: one 8-dword load");
+  struct Raw { u32x16_t l[3]; };
+  static_assert(sizeof(Raw) == sizeof(SJob), "SJob: three 16-dword loads");
+  Raw raw;
+  u32x8_t rs;
+  {
+    typedef const __attribute__((address_space(4))) char kchar;
+    kchar* kp = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
+    kchar* jp = kp + (size_t)min((int)blockIdx.z, MAXJ - 1) * sizeof(SJob);
+    asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dwordx16 %2, %4, 0x80\n\t"
+                 "s_load_dwordx8 %3, %5, %6"
+                 : "=&s"(raw.l[0]), "=&s"(raw.l[1]), "=&s"(raw.l[2]), "=&s"(rs)
+                 : "s"(jp), "s"(kp), "n"(MAXJ * sizeof(SJob)));
+  }
+  unsigned pre[NPRE];
+  lane_addresses(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, smem, pre);
+  {
+    u32x4_t pa = {pre[0], pre[1], pre[2], pre[3]}, pb = {pre[4], pre[5], pre[6], pre[7]};
+    u32x2_t pc = {pre[8], pre[9]};
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 : "+s"(raw.l[0]), "+s"(raw.l[1]), "+s"(raw.l[2]), "+s"(rs), "+v"(pa), "+v"(pb), "+v"(pc));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { pre[i] = pa[i]; pre[4 + i] = pb[i]; }
+    pre[8] = pc[0]; pre[9] = pc[1];
+  }
+  SJob J = __builtin_bit_cast(SJob, raw);
+  const int njobs = (int)rs[0], nbh = (int)rs[1];
+  const long long plane = (long long)(((unsigned long long)rs[3] << 32) | rs[2]);
+  const float* maxima = as_global((const float*)(((unsigned long long)rs[5] << 32) | rs[4]));
+  // a pointer that went through the statement is a generic one: say again that it is global memory,
+  // so its loads stay global_load / buffer_store (a flat load also counts on lgkmcnt)
+  for (int t = 0; t < 2; ++t) { J.a[t].p = as_global(J.a[t].p); J.b[t].p = as_global(J.b[t].p); }
+  J.e1 = as_global(J.e1); J.e2 = as_global(J.e2); J.c = as_global(J.c); J.cf = as_global(J.cf);
+  J.c2 = as_global(J.c2); J.c3 = as_global(J.c3);
+  const int head = blockIdx.x, tile = blockIdx.y;
+  const int u = tile * nbh + head;
+  if (AUX && blockIdx.z == (unsigned)njobs) {
     // the A3 combine row: three 256-thread groups per workgroup, one item (head, 8 queries) each
     A3CombineLds* lds = (A3CombineLds*)smem;
     const int g = threadIdx.x >> 8, t = threadIdx.x & 255;
-    const int item = blockIdx.x * (NTHREADS / 256) + g;
+    const int item = u * (NTHREADS / 256) + g;
     const bool active = item < L.a3.nbh * 32;
     const int bh = active ? item >> 5 : 0, qy = item & 31;
     const A3CombineState st = a3_combine_phase1(L.a3, bh, qy, t, lds[g], active);
@@ -499,19 +606,15 @@ __global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
     a3_combine_phase2(L.a3, bh, qy, t, lds[g], st, active);
     return;
   }
-  const SJob& J = L.j[blockIdx.y];
-  const int u = blockIdx.x;
-  const int nbh = L.nbh;
-  const int head = u % nbh, tile = u / nbh;
   if (J.kind == KIND_ABSSUMS) {
-    if (u < 2 * nbh) abssums(L, head, tile, (float*)smem);
+    if (tile < 2) abssums(L, head, tile, (float*)smem);
     return;
   }
   unsigned long long* so = nullptr;
 #ifdef TM_DIAG
-  if (L.stamps) so = L.stamps + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4 * 8;
+  if (L.stamps) so = L.stamps + ((size_t)blockIdx.z * 16 * nbh + u) * 4 * 8;
 #endif
-  stage_tile<DOT>(J, nbh, L.plane, L.maxima, head, tile, smem, so, DOT && (int)blockIdx.y == L.njobs - 1);
+  stage_tile<DOT>(J, nbh, plane, maxima, head, tile, smem, pre, so, t0, t1, DOT && (int)blockIdx.z == njobs - 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -782,9 +885,9 @@ struct Launcher {
   bool dot = false;   // the last job's e2 / cf carry the c-gradient dot (job_dotx / job_dot_part)
   void add(const SJob& j) { L.j[L.njobs++] = j; }
   int go(hipStream_t st) {
-    dim3 grid(16 * L.nbh, L.njobs);
+    dim3 grid(L.nbh, 16, L.njobs);
     if (L.a3.w) {   // one more row for the A3 combine: ceil(nbh * 32 / 3) <= 16 nbh items
-      grid.y += 1;
+      grid.z += 1;
       tm_allow_smem(pinv_stage_kernel<true>, STAGE_LDS + EPI_LDS);
       pinv_stage_kernel<true><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(L);
     } else if (dot) {   // the backward's last level: the c-gradient dot in its epilogue
@@ -796,7 +899,7 @@ struct Launcher {
     }
     TM_CHECK_LAUNCH();
 #ifdef TM_DIAG
-    if (g_split_stamps) g_split_stamps += (size_t)grid.x * grid.y * 4 * 8;  // the next launch's stamps follow
+    if (g_split_stamps) g_split_stamps += (size_t)grid.x * grid.y * grid.z * 4 * 8;  // the next launch's stamps follow
 #endif
     return 0;
   }
