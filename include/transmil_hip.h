@@ -477,6 +477,46 @@ int tm_clam_bwd(const float* Z, const float* H, const float* A_raw, const float*
                 float* dWic, float* dbic, void* stream);
 int tm_clam_relu_bwd(float* dh, const float* h, long long count, void* stream);
 
+/* ---- DTFD-MIL double-tier pseudo-bag pooling (dtfd.hip) -- code/models/model_interface_dtfd.py:174-279,
+ * code/models/DTFDMIL.py:14-109 ----
+ * fp32.  H [G S, L] = ReLU(xg W1^T) and Z [G S, 2D] = H [Wv;Wu]^T + [bv;bu] are the caller's GEMMs over
+ * the G S gathered rows (pseudo-bag g = rows g S .. g S + S - 1).  Limits: L == 512, D a multiple of 4
+ * and <= 512, 1 <= C <= 8, 1 <= S <= 1024, 1 <= G <= 64; anything else is refused before a launch.
+ * tm_dtfd_fwd (two launches): tier 1 per pseudo-bag, a_i = w . (tanh(Z[i, :D]) * sigmoid(Z[i, D:])) + b,
+ * p1 [G, S] = softmax_S(a) (max-shifted), M [G, L] = sum_i p_i h_i, sub [G, C] = M Wc^T + bc and, when
+ * cam is not NULL, cam [G, S, C] = p_i (h_i . Wc[c]); tier 2 over the rows of M with the attCls
+ * parameters (Wv2 / Wu2 [D, L], bv2 / bu2 [D], w2 [D], b2 [1], Wc2 [C, L], bc2 [C]): Z2 [G, 2D] (the gate
+ * pre-activations, saved for the backward), p2 [G] = softmax_G, F [L] = sum_g p2_g M_g, slide [C] =
+ * Wc2 F + bc2, yprob [C] = softmax(slide), yhat [1] = the first argmax; with label (device int64 [1],
+ * nullable) losses [2] = {mean_g CE(sub_g, y), CE(slide, y)}, NaN for a label outside [0, C).
+ * tm_dtfd_bwd: from dsub [G, C], dslide [C], gsub [1], gslide [1] (the gradients of sub, slide and the
+ * two losses; each nullable: zero).  need_t2: the attCls gradients dWv2, dbv2, dWu2, dbu2, dw2, db2,
+ * dWc2, dbc2 (one launch).  need_t1: dZ [G S, 2D], dH [G S, L] = p_i dM_g (the caller's GEMM then adds
+ * dZ [Wv;Wu]), dw [D], db [1], dWc [C, L], dbc [C] (two more launches).  Neither: no launch.  Every sum
+ * has one fixed order (no float atomics): bitwise repeatable.  work is sized by the query (0 for a
+ * shape outside the limits).
+ * tm_dtfd_relu: h = max(h, 0) in place (count a multiple of 4).  tm_dtfd_scatter_rows: dst[idx[r]] =
+ * src[r] for nrows rows of F floats by plain stores (idx int64 on the device, distinct; a row id
+ * outside [0, N) is skipped). */
+int tm_dtfd_fwd(const float* Z, const float* H, int G, int S, int L, int D, int C, const float* w,
+                const float* b, const float* Wc, const float* bc, const float* Wv2, const float* bv2,
+                const float* Wu2, const float* bu2, const float* w2, const float* b2, const float* Wc2,
+                const float* bc2, const long long* label, float* p1, float* M, float* sub, float* cam,
+                float* Z2, float* p2, float* F, float* slide, float* losses, float* yprob,
+                long long* yhat, void* stream);
+long long tm_dtfd_bwd_workspace(int G, int D, int C);
+int tm_dtfd_bwd(const float* Z, const float* H, const float* p1, const float* M, const float* p2,
+                const float* Z2, const float* F, const float* sub, const float* slide,
+                const long long* label, int G, int S, int L, int D, int C, const float* w, const float* Wc,
+                const float* Wv2, const float* Wu2, const float* w2, const float* Wc2, const float* dsub,
+                const float* dslide, const float* gsub, const float* gslide, int need_t1, int need_t2,
+                float* work, float* dZ, float* dH, float* dw, float* db, float* dWc, float* dbc,
+                float* dWv2, float* dbv2, float* dWu2, float* dbu2, float* dw2, float* db2, float* dWc2,
+                float* dbc2, void* stream);
+int tm_dtfd_relu(float* h, long long count, void* stream);
+int tm_dtfd_scatter_rows(const float* src, const long long* idx, int nrows, int F, long long N, float* dst,
+                         void* stream);
+
 /* ---- feature-bag sampling (bags.hip) -- code/datasets/feature_dataloader.py:335-431 ----
  * dst[r] = src[i0[r]] (i1 NULL or i1[r] < 0), (src[i0[r]] * wa[r]) + (src[i1[r]] * wb[r]) (mixup),
  * or 0 (i0[r] < 0); src [*, F] and dst [nrows, F] of dtype TM_F32 / TM_BF16, i0/i1 int64 row

@@ -157,6 +157,11 @@ _SIGS = {
     "tm_clam_bwd_workspace": (L, [I, I, I, I]),
     "tm_clam_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
     "tm_clam_relu_bwd": (I, [P, P, L, P]),
+    "tm_dtfd_fwd": (I, [P, P, I, I, I, I, I] + [P] * 25),
+    "tm_dtfd_bwd_workspace": (L, [I, I, I]),
+    "tm_dtfd_bwd": (I, [P] * 10 + [I] * 5 + [P] * 10 + [I, I] + [P] * 16),
+    "tm_dtfd_relu": (I, [P, L, P]),
+    "tm_dtfd_scatter_rows": (I, [P, P, I, I, L, P, P]),
     "tm_put_cls": (I, [P, I, I, I, P, P]),
     "tm_step_prepare": (I, [I, C.POINTER(CastTable), P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, P]),
     "tm_reduce_queue_create": (P, []),

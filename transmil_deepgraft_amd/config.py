@@ -161,3 +161,15 @@ def build_task(cfg, model, n_gpus: int = 1):
                         weight_decay=float(opt.weight_decay if opt.weight_decay is not None else 0.01),
                         loss=(cfg.Loss or {}).get("base_loss") or "CrossEntropyLoss", accumulate_grad_batches=acc)
     return task
+
+
+def build_dtfd_task(cfg, device="cuda"):
+    """``dtfd.DTFDTask`` for ``DeepGraft/DTFDMIL_*.yaml``.  ``ModelInterface_DTFD`` owns the parameters
+    and ``models.DTFDMIL`` is no model class (model_interface_dtfd.py:162-165), so this model does not go
+    through ``build_model``.  Read: ``Model.n_classes`` and, where given, ``Model.bag_size`` and
+    ``Model.max_pseudo_bags``; the bags are 1024 wide (``self.out_features``, :110) whatever
+    ``Model.in_features`` says, and the optimizers are the module's own two Adam (:594-601), not
+    ``Optimizer.*``."""
+    from .dtfd import DTFDMIL, DTFDTask
+    kw = {k: int(cfg.Model[k]) for k in ("bag_size", "max_pseudo_bags") if cfg.Model.get(k) is not None}
+    return DTFDTask(DTFDMIL(int(cfg.Model.n_classes), **kw).to(device))
