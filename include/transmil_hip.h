@@ -459,8 +459,8 @@ int tm_chowder_bwd(int dtype, const void* x, int B, int N, int L, const float* w
  * dH [N, L] = sum_c p dM[c] plus the instance classifiers' contributions to the selected rows (the
  * caller's GEMM then adds dZ [Wa;Wb]), dWc [K, D], dbc [K], dWcls [K, L], dbcls [K] and, with idx
  * (nullable: no instance evaluation), dWic [K, 2, L] and dbic [K, 2].  Every sum has one fixed order
- * (no float atomics): bitwise repeatable.  tm_clam_relu_bwd: dh = h > 0 ? dh : 0 in place (count a
- * multiple of 4).  work is sized by the queries (0 for a shape outside the limits). */
+ * (no float atomics): bitwise repeatable.  work is sized by the queries (0 for a shape outside the
+ * limits). */
 long long tm_clam_fwd_workspace(int N, int K);
 int tm_clam_scores(const float* Z, int N, int D, int K, const float* Wc, const float* bc, float* A_raw,
                    void* stream);
@@ -475,7 +475,6 @@ int tm_clam_bwd(const float* Z, const float* H, const float* A_raw, const float*
                 const int* idx, const float* dil, int k_sample, const float* dlogits, const float* dloss,
                 float* work, float* dZ, float* dH, float* dWc, float* dbc, float* dWcls, float* dbcls,
                 float* dWic, float* dbic, void* stream);
-int tm_clam_relu_bwd(float* dh, const float* h, long long count, void* stream);
 
 /* ---- DTFD-MIL double-tier pseudo-bag pooling (dtfd.hip) -- code/models/model_interface_dtfd.py:174-279,
  * code/models/DTFDMIL.py:14-109 ----
@@ -494,10 +493,7 @@ int tm_clam_relu_bwd(float* dh, const float* h, long long count, void* stream);
  * dWc2, dbc2 (one launch).  need_t1: dZ [G S, 2D], dH [G S, L] = p_i dM_g (the caller's GEMM then adds
  * dZ [Wv;Wu]), dw [D], db [1], dWc [C, L], dbc [C] (two more launches).  Neither: no launch.  Every sum
  * has one fixed order (no float atomics): bitwise repeatable.  work is sized by the query (0 for a
- * shape outside the limits).
- * tm_dtfd_relu: h = max(h, 0) in place (count a multiple of 4).  tm_dtfd_scatter_rows: dst[idx[r]] =
- * src[r] for nrows rows of F floats by plain stores (idx int64 on the device, distinct; a row id
- * outside [0, N) is skipped). */
+ * shape outside the limits). */
 int tm_dtfd_fwd(const float* Z, const float* H, int G, int S, int L, int D, int C, const float* w,
                 const float* b, const float* Wc, const float* bc, const float* Wv2, const float* bv2,
                 const float* Wu2, const float* bu2, const float* w2, const float* b2, const float* Wc2,
@@ -513,9 +509,6 @@ int tm_dtfd_bwd(const float* Z, const float* H, const float* p1, const float* M,
                 float* work, float* dZ, float* dH, float* dw, float* db, float* dWc, float* dbc,
                 float* dWv2, float* dbv2, float* dWu2, float* dbu2, float* dw2, float* db2, float* dWc2,
                 float* dbc2, void* stream);
-int tm_dtfd_relu(float* h, long long count, void* stream);
-int tm_dtfd_scatter_rows(const float* src, const long long* idx, int nrows, int F, long long N, float* dst,
-                         void* stream);
 
 /* ---- feature-bag sampling (bags.hip) -- code/datasets/feature_dataloader.py:335-431 ----
  * dst[r] = src[i0[r]] (i1 NULL or i1[r] < 0), (src[i0[r]] * wa[r]) + (src[i1[r]] * wb[r]) (mixup),
@@ -524,6 +517,10 @@ int tm_dtfd_scatter_rows(const float* src, const long long* idx, int nrows, int 
  * FeatureBagLoader.__getitem__ (:346-362) and data_interface.simple_collate's stack (:238-246). */
 int tm_gather_rows(int dtype, const void* src, int F, const long long* i0, const long long* i1,
                    const float* wa, const float* wb, int nrows, void* dst, void* stream);
+/* The inverse, fp32: dst[idx[r]] = src[r] for nrows rows of F floats by plain stores (idx int64 on the
+ * device, distinct; a row id outside [0, N) is skipped). */
+int tm_scatter_rows(const float* src, const long long* idx, int nrows, int F, long long N, float* dst,
+                    void* stream);
 
 /* ---- tile-bag ingest (tiles.hip) -- code/datasets/jpg_dataloader.py:164-171, 229-293 ----
  * dst[r][c][h][w] = lut[c][src[idx[r]][h][w][c]] rounded to dtype (ToTensor + Normalize as a
@@ -568,6 +565,10 @@ int tm_add_relu(int dtype, const void* a, const void* b, void* y, long long coun
 /* y[r, c] = act(y[r, c] + bias[c]) in place over rows x C channels-last (C % 8 == 0; act = ReLU
  * when relu != 0): a 3x3 convolution's folded conv+BN bias + ReLU (ResNet.py:95-104) in one pass */
 int tm_bias_act(int dtype, void* y, const void* bias, long long rows, int C, int relu, void* stream);
+/* fp32 ReLU passes in place over count elements (a multiple of 4, 16-B aligned): h = max(h, 0), the
+ * ReLU of a Linear without a bias, and its backward dh = h > 0 ? dh : 0 */
+int tm_relu(float* h, long long count, void* stream);
+int tm_relu_bwd(float* dh, const float* h, long long count, void* stream);
 /* ResNet stem tail (ResNet.py:240-245, BN folded into the convolution's bias): out[N, OH, OW, C] =
  * maxpool3x3/2 pad 1 (relu(y + bias)) over the raw channels-last bf16 stem output y[N, H, W, C],
  * OH = (H - 1) / 2 + 1; one pass instead of the in-place bias + ReLU and a max-pool launch */

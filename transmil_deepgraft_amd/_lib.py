@@ -142,6 +142,7 @@ _SIGS = {
     "tm_ppeg_bwd_workspace": (L, [I, I, I]),
     "tm_ppeg_bwd": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P, P, I, P, I, I, Fl, U64, P, P, P]),
     "tm_gather_rows": (I, [I, P, I, P, P, P, P, I, P, P]),
+    "tm_scatter_rows": (I, [P, P, I, I, L, P, P]),
     "tm_gather_tiles_u8": (I, [I, P, L, I, I, P, L, P, P, L, L, L, L, P]),
     "tm_attmil_fwd_workspace": (L, [I, I]),
     "tm_attmil_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
@@ -156,12 +157,9 @@ _SIGS = {
     "tm_clam_fwd": (I, [P, P, I, I, I, I, P, P, P, P, P, P, P, I, I, P, P, P, P, P, P, P, P, P, P, P]),
     "tm_clam_bwd_workspace": (L, [I, I, I, I]),
     "tm_clam_bwd": (I, [P, P, P, P, P, I, I, I, I, P, P, P, P, P, I, P, P, P, P, P, P, P, P, P, P, P, P]),
-    "tm_clam_relu_bwd": (I, [P, P, L, P]),
     "tm_dtfd_fwd": (I, [P, P, I, I, I, I, I] + [P] * 25),
     "tm_dtfd_bwd_workspace": (L, [I, I, I]),
     "tm_dtfd_bwd": (I, [P] * 10 + [I] * 5 + [P] * 10 + [I, I] + [P] * 16),
-    "tm_dtfd_relu": (I, [P, L, P]),
-    "tm_dtfd_scatter_rows": (I, [P, P, I, I, L, P, P]),
     "tm_put_cls": (I, [P, I, I, I, P, P]),
     "tm_step_prepare": (I, [I, C.POINTER(CastTable), P, P, P, P, P, P, I, P, P, P, P, P, P, I, I, P]),
     "tm_reduce_queue_create": (P, []),
@@ -173,6 +171,8 @@ _SIGS = {
     "tm_dropout_bwd_pad": (I, [I, P, I, I, I, I, I, Fl, U64, P, P, P]),
     "tm_add_relu": (I, [I, P, P, P, L, P]),
     "tm_bias_act": (I, [I, P, P, L, I, I, P]),
+    "tm_relu": (I, [P, L, P]),
+    "tm_relu_bwd": (I, [P, P, L, P]),
     "tm_bias_relu_maxpool": (I, [P, P, P, I, I, I, I, P]),
     "tm_bn_relu_maxpool": (I, [P, P, P, P, I, I, I, I, P]),
     "tm_stem_conv_pool": (I, [P, P, P, P, I, I, I, L, L, L, L, P]),

@@ -10,35 +10,12 @@
 // HBM-bound row passes over H [N, L] and Z [N, 2D]; every reduction is a fixed-order tree, so
 // results are deterministic run to run.
 #include "common.h"
+#include "mil_common.h"
 #include "../../include/transmil_hip.h"
 
 namespace {
 
 constexpr int POOL_ROWS = 64;     // rows of H per pooling / backward-row block
-
-TM_DEV float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-TM_DEV float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-
-// block-wide sum / max of one value per thread (blockDim.x multiple of 64, <= 1024)
-template <bool MAX>
-TM_DEV float block_reduce(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float u = __shfl_xor(v, o);
-    v = MAX ? fmaxf(v, u) : v + u;
-  }
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < nw; ++i) r = MAX ? fmaxf(r, red[i]) : r + red[i];
-  return r;
-}
 
 // one wave per instance row: a_i = sum_d tanh(Z[i][d]) sigmoid(Z[i][D+d]) w[d] + b
 __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ Z, int N, int D,
@@ -48,7 +25,7 @@ __global__ void __launch_bounds__(256) score_kernel(const float* __restrict__ Z,
   if (i >= N) return;
   const float* z = Z + (size_t)i * 2 * D;
   float acc = 0.f;
-  for (int d = lane; d < D; d += 64) acc += tanhf(z[d]) * sigmoidf_(z[D + d]) * w[d];
+  for (int d = lane; d < D; d += 64) acc += tanhf(z[d]) * sigmoid_fast(z[D + d]) * w[d];
   acc = wave_sum(acc);
   if (lane == 0) a[i] = acc + b[0];
 }
@@ -166,7 +143,7 @@ __global__ void __launch_bounds__(256) bwd_rows_kernel(const float* __restrict__
     const float* z = Z + (size_t)i * 2 * D;
     float* gz = dZ + (size_t)i * 2 * D;
     for (int d = lane; d < D; d += 64) {
-      const float t = tanhf(z[d]), sg = sigmoidf_(z[D + d]), wd = w[d];
+      const float t = tanhf(z[d]), sg = sigmoid_fast(z[D + d]), wd = w[d];
       gz[d] = da * wd * sg * (1.f - t * t);
       gz[D + d] = da * wd * t * sg * (1.f - sg);
       sm[wv * D + d] += da * t * sg;

@@ -63,6 +63,21 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const T* __restrict__ 
   }
 }
 
+// dst[idx[r]] = src[r] (rows of F floats); a row id outside [0, N) is skipped
+__global__ void __launch_bounds__(256) scatter_rows_kernel(const float* __restrict__ src,
+                                                           const long long* __restrict__ idx, int F, long long N,
+                                                           float* __restrict__ dst) {
+  const long long row = idx[blockIdx.x];
+  if (row < 0 || row >= N) return;
+  const float* s = src + (size_t)blockIdx.x * F;
+  float* d = dst + (size_t)row * F;
+  if (F % 4 == 0) {                                   // rows 16-B aligned (the entry point checks the bases)
+    for (int c = threadIdx.x; c < F / 4; c += 256) ((f32x4*)d)[c] = ((const f32x4*)s)[c];
+    return;
+  }
+  for (int c = threadIdx.x; c < F; c += 256) d[c] = s[c];
+}
+
 }  // namespace
 
 extern "C" int tm_gather_rows(int dtype, const void* src, int F, const long long* i0, const long long* i1,
@@ -82,6 +97,16 @@ extern "C" int tm_gather_rows(int dtype, const void* src, int F, const long long
     tm_set_error("gather_rows: dtype must be TM_F32 or TM_BF16");
     return 1;
   }
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tm_scatter_rows(const float* src, const long long* idx, int nrows, int F, long long N, float* dst,
+                               void* stream) {
+  TM_REQUIRE(src && idx && dst && nrows >= 0 && F > 0 && N >= 0, "scatter_rows: bad args");
+  TM_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "scatter_rows: 16-B aligned buffers");
+  if (nrows == 0) return 0;
+  scatter_rows_kernel<<<nrows, 256, 0, (hipStream_t)stream>>>(src, idx, F, N, dst);
   TM_CHECK_LAUNCH();
   return 0;
 }

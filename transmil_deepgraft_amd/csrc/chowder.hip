@@ -19,8 +19,8 @@
 //   bwd_params_kernel    one thread per weight-gradient element / per column of dw, summing over the
 //                        bags in order (b, then j); further workgroups write the selected rows of dx
 // No float atomics anywhere: every sum has one fixed order, so results are bitwise repeatable.
-#include <limits.h>
 #include "common.h"
+#include "mil_common.h"
 #include "../../include/transmil_hip.h"
 
 namespace {
@@ -113,25 +113,6 @@ __global__ void __launch_bounds__(SCORE_THREADS) score_select_kernel(
   }
 }
 
-struct Pair {
-  float v;
-  int i;
-};
-// ascending order (score, index) and descending-score order (ties: lower index first)
-TM_DEV bool before_min(float v, int i, Pair p) { return v < p.v || (v == p.v && i < p.i); }
-TM_DEV bool before_max(float v, int i, Pair p) { return v > p.v || (v == p.v && i < p.i); }
-
-template <bool MAXSIDE>
-TM_DEV Pair wave_first(Pair p) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(p.v, o, 64);
-    const int i = __shfl_xor(p.i, o, 64);
-    if (MAXSIDE ? before_max(v, i, p) : before_min(v, i, p)) p = {v, i};
-  }
-  return p;
-}
-
 // sum_k A[k * sa] * v[k] over a group of GL neighbouring lanes: lane `sub` of the group adds k = sub,
 // sub + GL, ... in order, then the group's xor butterfly (every lane of the group gets the sum).
 // Every lane of the wave must call it (`on` false: contributes nothing); the loads of one lane are
@@ -171,7 +152,6 @@ TM_DEV void affine(const float* __restrict__ W, const float* __restrict__ bias, 
 // sel / sel_i [2R] (LDS) receive the selected scores and indices.
 TM_DEV void select_rounds(const float* cv, const int* ci, int nchunks, int N, int R, Pair (*red)[2][MERGE_WAVES],
                           float* sel, int* sel_i) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   Pair last_lo = {-INFINITY, -1}, last_hi = {INFINITY, -1};
   for (int k = 0; k < R; ++k) {
     Pair lo = {INFINITY, INT_MAX}, hi = {-INFINITY, INT_MAX};
@@ -184,29 +164,14 @@ TM_DEV void select_rounds(const float* cv, const int* ci, int nchunks, int N, in
       if (before_min(last_lo.v, last_lo.i, Pair{vl, il}) && before_min(vl, il, lo)) lo = {vl, il};
       if (before_max(last_hi.v, last_hi.i, Pair{vh, ih}) && before_max(vh, ih, hi)) hi = {vh, ih};
     }
-    lo = wave_first<false>(lo);
-    hi = wave_first<true>(hi);
-    Pair(*r)[MERGE_WAVES] = red[k & 1];           // two buffers: one barrier per round
-    if (lane == 0) {
-      r[0][wave] = lo;
-      r[1][wave] = hi;
-    }
-    __syncthreads();
-    lo = r[0][0];
-    hi = r[1][0];
-#pragma unroll
-    for (int u = 1; u < MERGE_WAVES; ++u) {
-      const Pair a = r[0][u], c = r[1][u];
-      if (before_min(a.v, a.i, lo)) lo = a;
-      if (before_max(c.v, c.i, hi)) hi = c;
-    }
-    last_lo = lo;
-    last_hi = hi;
+    const PairLoHi got = select_round_tail<MERGE_WAVES>(lo, hi, red[k & 1]);   // two buffers: one barrier per round
+    last_lo = got.lo;
+    last_hi = got.hi;
     if (threadIdx.x == 0) {
-      sel[k] = lo.v;
-      sel[R + k] = hi.v;
-      sel_i[k] = min(max(lo.i, 0), N - 1);        // in range whatever the scores were (NaN / Inf input)
-      sel_i[R + k] = min(max(hi.i, 0), N - 1);
+      sel[k] = got.lo.v;
+      sel[R + k] = got.hi.v;
+      sel_i[k] = select_clamp(got.lo.i, N);
+      sel_i[R + k] = select_clamp(got.hi.i, N);
     }
   }
   __syncthreads();

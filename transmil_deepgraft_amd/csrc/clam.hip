@@ -28,8 +28,8 @@
 //                     contributions of row i in list order; block partials of dWc / dbc
 //   bwd_reduce_kernel dWc, dbc = the block partials added in block order
 // No float atomics: every sum is a fixed tree or an index-ordered loop, so results repeat bitwise.
-#include <limits.h>
 #include "common.h"
+#include "mil_common.h"
 #include "../../include/transmil_hip.h"
 
 namespace {
@@ -42,26 +42,6 @@ constexpr int RB_MAX = 512;       // rows per row-pass block
 constexpr int FIN_THREADS = 1024;
 constexpr int FIN_WAVES = FIN_THREADS / 64;
 constexpr int FIN_SLICES = FIN_THREADS / (CL / 4);   // 8 groups of 128 f32x4 columns
-
-TM_DEV float sigmoid_(float x) { return 1.f / (1.f + expf(-x)); }
-TM_DEV float dot4(f32x4 a, f32x4 b, float acc) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc = fmaf(a[u], b[u], acc);
-  return acc;
-}
-
-// block-wide sum / max of one value per thread, the same fixed order every run (red: >= 16 floats)
-template <bool MAX>
-TM_DEV float block_reduce(float v, float* red) {
-  v = MAX ? wave_max(v) : wave_sum(v);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int i = 1; i < nw; ++i) r = MAX ? fmaxf(r, red[i]) : r + red[i];
-  return r;
-}
 
 // Forward row pass, compiled for KT = 2, 4, 8 classes (the smallest KT >= K: the per-class
 // accumulators are registers, classes K..KT-1 carry zero weights and are never stored).
@@ -90,9 +70,7 @@ __global__ void __launch_bounds__(256) rows_fwd_kernel(const float* __restrict__
     for (int c = 0; c < KT; ++c) acc[c] = 0.f;
     for (int d = 4 * lane; d < D; d += 256) {
       const f32x4 za = *(const f32x4*)(z + d), zb = *(const f32x4*)(z + D + d);
-      f32x4 g;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) g[u] = tanhf(za[u]) * sigmoid_(zb[u]);
+      const f32x4 g = gate(za, zb);
 #pragma unroll
       for (int c = 0; c < KT; ++c) acc[c] = dot4(g, *(const f32x4*)(wcs + c * D + d), acc[c]);
     }
@@ -162,30 +140,10 @@ __global__ void __launch_bounds__(256) rows_fwd_kernel(const float* __restrict__
   }
 }
 
-struct Pair {
-  float v;
-  int i;
-};
-// descending-score order and ascending-score order; ties: the lower index first
-TM_DEV bool before_max(float v, int i, Pair p) { return v > p.v || (v == p.v && i < p.i); }
-TM_DEV bool before_min(float v, int i, Pair p) { return v < p.v || (v == p.v && i < p.i); }
-
-template <bool MAXSIDE>
-TM_DEV Pair wave_first(Pair p) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float v = __shfl_xor(p.v, o, 64);
-    const int i = __shfl_xor(p.i, o, 64);
-    if (MAXSIDE ? before_max(v, i, p) : before_min(v, i, p)) p = {v, i};
-  }
-  return p;
-}
-
 // k rounds over one class's N scores: round r takes, on each side, the first pair in that side's
 // order that comes after the pair taken in round r - 1.  sel_hi / sel_lo [k] (LDS) receive the indices.
 TM_DEV void select_rounds(const float* __restrict__ a, int N, int k, Pair (*red)[2][FIN_WAVES], int* sel_hi,
                           int* sel_lo) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   Pair last_hi = {INFINITY, -1}, last_lo = {-INFINITY, -1};
   for (int r = 0; r < k; ++r) {
     Pair hi = {-INFINITY, INT_MAX}, lo = {INFINITY, INT_MAX};
@@ -194,27 +152,12 @@ TM_DEV void select_rounds(const float* __restrict__ a, int N, int k, Pair (*red)
       if (before_max(last_hi.v, last_hi.i, Pair{v, i}) && before_max(v, i, hi)) hi = {v, i};
       if (before_min(last_lo.v, last_lo.i, Pair{v, i}) && before_min(v, i, lo)) lo = {v, i};
     }
-    hi = wave_first<true>(hi);
-    lo = wave_first<false>(lo);
-    Pair(*q)[FIN_WAVES] = red[r & 1];             // two buffers: one barrier per round
-    if (lane == 0) {
-      q[0][wave] = hi;
-      q[1][wave] = lo;
-    }
-    __syncthreads();
-    hi = q[0][0];
-    lo = q[1][0];
-#pragma unroll
-    for (int u = 1; u < FIN_WAVES; ++u) {
-      const Pair x = q[0][u], y = q[1][u];
-      if (before_max(x.v, x.i, hi)) hi = x;
-      if (before_min(y.v, y.i, lo)) lo = y;
-    }
-    last_hi = hi;
-    last_lo = lo;
+    const PairLoHi got = select_round_tail<FIN_WAVES>(lo, hi, red[r & 1]);   // two buffers: one barrier per round
+    last_hi = got.hi;
+    last_lo = got.lo;
     if (threadIdx.x == 0) {
-      sel_hi[r] = min(max(hi.i, 0), N - 1);       // in range whatever the scores were (NaN / Inf input)
-      sel_lo[r] = min(max(lo.i, 0), N - 1);
+      sel_hi[r] = select_clamp(got.hi.i, N);
+      sel_lo[r] = select_clamp(got.lo.i, N);
     }
   }
   __syncthreads();
@@ -297,8 +240,8 @@ __global__ void __launch_bounds__(FIN_THREADS) finalize_kernel(
     __syncthreads();
     if (t < nsel) {
       const int tgt = (pos && t < k) ? 1 : 0;
-      const float l0 = il[t][0], l1 = il[t][1], mx = fmaxf(l0, l1);
-      const float lse = mx + logf(expf(l0 - mx) + expf(l1 - mx));
+      const float l0 = il[t][0], l1 = il[t][1];
+      const float lse = lse_of(il[t], 2);
       const float scale = (subtyping ? 1.f / (float)K : 1.f) / (float)nsel;
       lossj[t] = lse - (tgt ? l1 : l0);
       const int e = c * k2 + t;
@@ -456,8 +399,9 @@ __global__ void __launch_bounds__(256) rows_bwd_kernel(
         f32x4 ga, gb;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          ga[u] = dg[u] * sg[u] * (1.f - th[u] * th[u]);
-          gb[u] = dg[u] * th[u] * sg[u] * (1.f - sg[u]);
+          const GateGrad gz4 = gate_bwd(dg[u], th[u], sg[u]);
+          ga[u] = gz4.a;
+          gb[u] = gz4.b;
         }
         *(f32x4*)(gz + d) = ga;
         *(f32x4*)(gz + D + d) = gb;
@@ -498,18 +442,6 @@ __global__ void __launch_bounds__(256) bwd_reduce_kernel(const float* __restrict
     for (int b = 0; b < nblk; ++b) s += dbc_part[(size_t)b * K + e - KD];
     dbc[e - KD] = s;
   }
-}
-
-// dh = h > 0 ? dh : 0 in place, four elements per thread
-__global__ void __launch_bounds__(256) relu_bwd_kernel(float* __restrict__ dh, const float* __restrict__ h,
-                                                       long long n4) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 g = ((const f32x4*)dh)[i];
-  const f32x4 x = ((const f32x4*)h)[i];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) g[u] = x[u] > 0.f ? g[u] : 0.f;
-  ((f32x4*)dh)[i] = g;
 }
 
 // rows per row-pass workgroup: at most 512 workgroups up to N = 262144, at least 16 rows each
@@ -622,16 +554,6 @@ extern "C" int tm_clam_bwd(const float* Z, const float* H, const float* A_raw, c
     rows_bwd_kernel<8><<<nblk, 256, lds, st>>>(Z, H, A_raw, stats, N, D, K, RB, Wc, dM, rv, lrow, lvec, nlist, dZ, dH,
                                                dwc_part, dbc_part);
   bwd_reduce_kernel<<<(K * D + K + 255) / 256, 256, 0, st>>>(dwc_part, dbc_part, nblk, K * D, K, dWc, dbc);
-  TM_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int tm_clam_relu_bwd(float* dh, const float* h, long long count, void* stream) {
-  TM_REQUIRE(dh && h && count >= 0 && count % 4 == 0, "clam_relu_bwd: count must be a multiple of 4");
-  TM_REQUIRE(((uintptr_t)dh % 16) == 0 && ((uintptr_t)h % 16) == 0, "clam_relu_bwd: 16-B aligned buffers");
-  if (count == 0) return 0;
-  const long long n4 = count / 4;
-  relu_bwd_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(dh, h, n4);
   TM_CHECK_LAUNCH();
   return 0;
 }

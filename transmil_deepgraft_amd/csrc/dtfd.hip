@@ -30,6 +30,7 @@
 //   t1_reduce_kernel  dw, db = the pseudo-bags' partials added in order.
 // No float atomics: every sum is a fixed tree or an index-ordered loop, so results repeat bitwise.
 #include "common.h"
+#include "mil_common.h"
 #include "../../include/transmil_hip.h"
 
 namespace {
@@ -44,36 +45,6 @@ constexpr int NW = NT / 64;
 constexpr int SLICES = NT / (CL / 4);   // 8 groups of 128 f32x4 columns
 constexpr int MCHUNK = 16;        // rows of M staged per step of the tier-2 gate products
 constexpr int T2_D = NW / 2;      // gate columns per tier-2 backward workgroup: one weight row per wave
-
-TM_DEV float sigmoid_(float x) { return 1.f / (1.f + expf(-x)); }
-TM_DEV float dot4(f32x4 a, f32x4 b, float acc) {
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc = fmaf(a[u], b[u], acc);
-  return acc;
-}
-
-// block-wide sum / max of one value per thread, the same fixed order every run (red: NW floats)
-template <bool MAX>
-TM_DEV float block_reduce(float v, float* red) {
-  v = MAX ? wave_max(v) : wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float r = red[0];
-#pragma unroll
-  for (int i = 1; i < NW; ++i) r = MAX ? fmaxf(r, red[i]) : r + red[i];
-  return r;
-}
-
-// log-sum-exp of C values, max-shifted
-TM_DEV float lse_of(const float* v, int C) {
-  float mx = v[0];
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, v[c]);
-  float s = 0.f;
-  for (int c = 0; c < C; ++c) s += expf(v[c] - mx);
-  return mx + logf(s);
-}
 
 __global__ void __launch_bounds__(NT) t1_fwd_kernel(const float* __restrict__ Z, const float* __restrict__ H, int S,
                                                     int D, int C, const float* __restrict__ w,
@@ -98,10 +69,7 @@ __global__ void __launch_bounds__(NT) t1_fwd_kernel(const float* __restrict__ Z,
     float acc = 0.f;
     for (int d = 4 * lane; d < D; d += 256) {
       const f32x4 za = *(const f32x4*)(z + d), zb = *(const f32x4*)(z + D + d);
-      f32x4 gt;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) gt[u] = tanhf(za[u]) * sigmoid_(zb[u]);
-      acc = dot4(gt, *(const f32x4*)(ws + d), acc);
+      acc = dot4(gate(za, zb), *(const f32x4*)(ws + d), acc);
     }
     acc = wave_sum(acc);
     if (lane == 0) sc[j] = acc + b0;
@@ -109,14 +77,14 @@ __global__ void __launch_bounds__(NT) t1_fwd_kernel(const float* __restrict__ Z,
   __syncthreads();
   float m = -INFINITY;
   for (int j = t; j < S; j += NT) m = fmaxf(m, sc[j]);
-  m = block_reduce<true>(m, red);
+  m = block_reduce<true, NW>(m, red);
   float s = 0.f;
   for (int j = t; j < S; j += NT) {
     const float e = expf(sc[j] - m);
     sc[j] = e;
     s += e;
   }
-  s = block_reduce<false>(s, red);
+  s = block_reduce<false, NW>(s, red);
   const float inv = 1.f / s;
   for (int j = t; j < S; j += NT) {
     const float p = sc[j] * inv;
@@ -196,8 +164,8 @@ __global__ void __launch_bounds__(NT) t2_fwd_kernel(
           Z2[(size_t)(g0 + gg) * 2 * D + d] = zv;
           Z2[(size_t)(g0 + gg) * 2 * D + D + d] = zu;
         }
-        const float gate = tanhf(zv) * sigmoid_(zu);
-        if (lane == g0 + gg) acc_g = fmaf(gate, wd, acc_g);
+        const float gt = gate(zv, zu);
+        if (lane == g0 + gg) acc_g = fmaf(gt, wd, acc_g);
       }
     }
   }
@@ -323,8 +291,8 @@ __global__ void __launch_bounds__(NT) t2_bwd_kernel(
       float dz = 0.f;
       if (on) {
         const float th = tanhf(Z2[(size_t)g * 2 * D + d]), sg = sigmoid_(Z2[(size_t)g * 2 * D + D + d]);
-        const float dg = da2s[g] * wd;
-        dz = which == 0 ? dg * sg * (1.f - th * th) : dg * th * sg * (1.f - sg);
+        const GateGrad gz = gate_bwd(da2s[g] * wd, th, sg);
+        dz = which == 0 ? gz.a : gz.b;
         wacc = fmaf(da2s[g], th * sg, wacc);
         bacc += dz;
         if (need_t2) {
@@ -447,8 +415,8 @@ __global__ void __launch_bounds__(NT) t1_bwd_kernel(
     num = fmaf(p, dps[j], num);
     den += p;
   }
-  num = block_reduce<false>(num, red);
-  den = block_reduce<false>(den, red);
+  num = block_reduce<false, NW>(num, red);
+  den = block_reduce<false, NW>(den, red);
   const float res = num / den;
   f32x4 dwacc[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   float dbacc = 0.f;
@@ -470,9 +438,10 @@ __global__ void __launch_bounds__(NT) t1_bwd_kernel(
         f32x4 ga, gb;
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const float th = tanhf(za[u]), sg = sigmoid_(zb[u]), dg = da * wd[u];
-          ga[u] = dg * sg * (1.f - th * th);
-          gb[u] = dg * th * sg * (1.f - sg);
+          const float th = tanhf(za[u]), sg = sigmoid_(zb[u]);
+          const GateGrad gz4 = gate_bwd(da * wd[u], th, sg);
+          ga[u] = gz4.a;
+          gb[u] = gz4.b;
           dwacc[ch][u] = fmaf(da, th * sg, dwacc[ch][u]);
         }
         *(f32x4*)(gz + d) = ga;
@@ -513,31 +482,6 @@ __global__ void __launch_bounds__(256) t1_reduce_kernel(const float* __restrict_
     for (int g = 0; g < G; ++g) s += dbpart[g];
     db[0] = s;
   }
-}
-
-// h = max(h, 0) in place, four elements per thread
-__global__ void __launch_bounds__(256) relu_kernel(float* __restrict__ h, long long n4) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f32x4 x = ((const f32x4*)h)[i];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) x[u] = fmaxf(x[u], 0.f);
-  ((f32x4*)h)[i] = x;
-}
-
-// dst[idx[r]] = src[r] (rows of F floats); a row id outside [0, N) is skipped
-__global__ void __launch_bounds__(256) scatter_rows_kernel(const float* __restrict__ src,
-                                                           const long long* __restrict__ idx, int F, long long N,
-                                                           float* __restrict__ dst) {
-  const long long row = idx[blockIdx.x];
-  if (row < 0 || row >= N) return;
-  const float* s = src + (size_t)blockIdx.x * F;
-  float* d = dst + (size_t)row * F;
-  if (F % 4 == 0) {                                   // rows 16-B aligned (the entry point checks the bases)
-    for (int c = threadIdx.x; c < F / 4; c += 256) ((f32x4*)d)[c] = ((const f32x4*)s)[c];
-    return;
-  }
-  for (int c = threadIdx.x; c < F; c += 256) d[c] = s[c];
 }
 
 const char* check_shape(int G, int S, int L, int D, int C) {
@@ -605,26 +549,6 @@ extern "C" int tm_dtfd_bwd(const float* Z, const float* H, const float* p1, cons
     t1_bwd_kernel<<<G, NT, 0, st>>>(Z, H, p1, M, p2, dFw, part, nb, dsubt, Wc, w, G, S, D, C, dZ, dH, dwpart, dbpart);
     t1_reduce_kernel<<<(D + 1 + 255) / 256, 256, 0, st>>>(dwpart, dbpart, G, D, dw, db);
   }
-  TM_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int tm_dtfd_relu(float* h, long long count, void* stream) {
-  TM_REQUIRE(h && count >= 0 && count % 4 == 0, "dtfd_relu: count must be a multiple of 4");
-  TM_REQUIRE(((uintptr_t)h % 16) == 0, "dtfd_relu: 16-B aligned buffer");
-  if (count == 0) return 0;
-  const long long n4 = count / 4;
-  relu_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(h, n4);
-  TM_CHECK_LAUNCH();
-  return 0;
-}
-
-extern "C" int tm_dtfd_scatter_rows(const float* src, const long long* idx, int nrows, int F, long long N, float* dst,
-                                    void* stream) {
-  TM_REQUIRE(src && idx && dst && nrows >= 0 && F > 0 && N >= 0, "dtfd_scatter_rows: bad args");
-  TM_REQUIRE(((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0, "dtfd_scatter_rows: 16-B aligned buffers");
-  if (nrows == 0) return 0;
-  scatter_rows_kernel<<<nrows, 256, 0, (hipStream_t)stream>>>(src, idx, F, N, dst);
   TM_CHECK_LAUNCH();
   return 0;
 }

@@ -226,6 +226,28 @@ __global__ __launch_bounds__(256) void bias_act_kernel(T* y, const T* __restrict
   store8<T>(y + i, o);
 }
 
+// h = max(h, 0) in place, four elements per thread
+__global__ void __launch_bounds__(256) relu_kernel(float* __restrict__ h, long long n4) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  f32x4 x = ((const f32x4*)h)[i];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) x[u] = fmaxf(x[u], 0.f);
+  ((f32x4*)h)[i] = x;
+}
+
+// dh = h > 0 ? dh : 0 in place, four elements per thread
+__global__ void __launch_bounds__(256) relu_bwd_kernel(float* __restrict__ dh, const float* __restrict__ h,
+                                                       long long n4) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  f32x4 g = ((const f32x4*)dh)[i];
+  const f32x4 x = ((const f32x4*)h)[i];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) g[u] = x[u] > 0.f ? g[u] : 0.f;
+  ((f32x4*)dh)[i] = g;
+}
+
 }  // namespace
 
 // CrossEntropyLoss(logits, one_hot(label).float()) averaged over the B rows
@@ -544,6 +566,26 @@ extern "C" int tm_add_relu(int dtype, const void* a, const void* b, void* y, lon
     tm_set_error("add_relu: dtype");
     return 1;
   }
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tm_relu(float* h, long long count, void* stream) {
+  TM_REQUIRE(h && count >= 0 && count % 4 == 0, "relu: count must be a multiple of 4");
+  TM_REQUIRE(((uintptr_t)h % 16) == 0, "relu: 16-B aligned buffer");
+  if (count == 0) return 0;
+  const long long n4 = count / 4;
+  relu_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(h, n4);
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tm_relu_bwd(float* dh, const float* h, long long count, void* stream) {
+  TM_REQUIRE(dh && h && count >= 0 && count % 4 == 0, "relu_bwd: count must be a multiple of 4");
+  TM_REQUIRE(((uintptr_t)dh % 16) == 0 && ((uintptr_t)h % 16) == 0, "relu_bwd: 16-B aligned buffers");
+  if (count == 0) return 0;
+  const long long n4 = count / 4;
+  relu_bwd_kernel<<<(unsigned)((n4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(dh, h, n4);
   TM_CHECK_LAUNCH();
   return 0;
 }

@@ -24,7 +24,8 @@ import torch.nn as nn
 
 from . import _lib
 from ._lib import F32
-from .engine import Pool, _p, _stream, colsum, gemm, weight_grad
+from .engine import Pool, _p, _stream
+from .gated import _f32c, device_label, embed, embed_bwd
 
 M_DIM = 512
 MAX_D = 512
@@ -32,10 +33,6 @@ MAX_CLASSES = 8
 MAX_BAG_SIZE = 1024
 MAX_PSEUDO_BAGS = 64
 _GATHER_ROWS = 65535          # tm_gather_rows' rows per launch
-
-
-def _f32c(t):
-    return t.detach().float().contiguous()
 
 
 class _DtfdFn(torch.autograd.Function):
@@ -59,11 +56,7 @@ class _DtfdFn(torch.autograd.Function):
         for s in range(0, R, _GATHER_ROWS):
             e = min(R, s + _GATHER_ROWS)
             _lib.call("tm_gather_rows", F32, _p(x), Fin, _p(idx[s:e]), None, None, None, e - s, _p(xg[s:e]), _stream())
-        h = torch.empty(R, L, device=dev)
-        gemm(xg, W1_, h, R, L, Fin, lda=Fin, ldb=Fin, ldc=L, dtype=F32, c_dtype=F32)
-        _lib.call("tm_dtfd_relu", _p(h), R * L, _stream())
-        Z = torch.empty(R, D2, device=dev)
-        gemm(h, Wvu, Z, R, D2, L, lda=L, ldb=L, ldc=D2, dtype=F32, c_dtype=F32, bias=bvu)
+        h, Z = embed(xg, W1_, None, Wvu, bvu)           # dimreduction.fc1 has no bias
         p1, M, sub = torch.empty(G, S, device=dev), torch.empty(G, L, device=dev), torch.empty(G, C, device=dev)
         cam = torch.empty(G, S, C, device=dev) if return_cam else None
         Z2, p2, F = torch.empty(G, D2, device=dev), torch.empty(G, device=dev), torch.empty(L, device=dev)
@@ -111,25 +104,13 @@ class _DtfdFn(torch.autograd.Function):
                   _p(dWv2), _p(dbv2), _p(dWu2), _p(dbu2), _p(dw2), _p(db2), _p(dWc2), _p(dbc2), _stream())
         dx = dW1 = dWvu = dbvu = None
         if need[0] or any(need[2:7]):
-            pool = Pool(dev)
-            # attention_V / attention_U: d[Wv;Wu] = dZ^T h, d[bv;bu] = colsum(dZ), dh += dZ [Wv;Wu]
-            dWvu = torch.empty(D2, L, device=dev)
-            weight_grad(dZ, h, dWvu, D2, L, R, ldy=D2, ldx=L, dtype=F32, work_pool=pool)
-            dbvu = torch.empty(D2, device=dev)
-            colsum(dZ, R, D2, D2, F32, dbvu, pool)
-            if need[0] or need[2]:
-                gemm(dZ, Wvu, dh, R, L, D2, lda=D2, ldb=L, ldc=L, b_kn=1, dtype=F32, c_dtype=F32, accumulate=True)
-                # the ReLU, then dimreduction.fc1 (no bias)
-                _lib.call("tm_clam_relu_bwd", _p(dh), _p(h), R * L, _stream())
-            if need[2]:
-                dW1 = torch.empty(L, Fin, device=dev)
-                weight_grad(dh, xg, dW1, L, Fin, R, ldy=L, ldx=Fin, dtype=F32, work_pool=pool)
+            # attention_V / attention_U, the ReLU, then dimreduction.fc1 (no bias)
+            dxg, dW1, _, dWvu, dbvu = embed_bwd(dZ, dh, h, xg, W1, Wvu, Pool(dev), need_dx=need[0], need_dW1=need[2],
+                                                need_db1=False)
             if need[0]:
                 # zero-filled, then plain stores at the selected rows (the permutation makes them distinct)
-                dxg = torch.empty(R, Fin, device=dev)
-                gemm(dh, W1, dxg, R, Fin, L, lda=L, ldb=Fin, ldc=Fin, b_kn=1, dtype=F32, c_dtype=F32)
                 dx = torch.zeros(N, Fin, device=dev)
-                _lib.call("tm_dtfd_scatter_rows", _p(dxg), _p(idx), R, Fin, N, _p(dx), _stream())
+                _lib.call("tm_scatter_rows", _p(dxg), _p(idx), R, Fin, N, _p(dx), _stream())
         split = (lambda t, lo: t[lo * D:(lo + 1) * D]) if dWvu is not None else (lambda t, lo: None)
         return (dx, None, dW1, split(dWvu, 0), split(dbvu, 0), split(dWvu, 1), split(dbvu, 1), dw, db, dWc, dbc,
                 dWv2, dbv2, dWu2, dbu2, dw2, db2, dWc2, dbc2, None, None, None, None)
@@ -197,9 +178,7 @@ def _pool(x, perm, W1, Wv, bv, Wu, bu, w, b, Wc, bc, Wv2, bv2, Wu2, bu2, w2, b2,
     if not perm.is_cuda or perm.dtype != torch.int64 or perm.dim() != 1 or perm.numel() < G * S:
         raise RuntimeError(f"DTFDMIL: perm must be a 1-D int64 GPU tensor of at least G S = {G * S} row ids")
     if label is not None:
-        if not label.is_cuda or label.dtype != torch.int64:
-            raise RuntimeError("DTFDMIL: label must be an int64 GPU tensor (it is read on the device)")
-        label = label.reshape(-1)
+        label = device_label(label, "DTFDMIL")
     idx = perm.detach()[:G * S].contiguous()
     return _DtfdFn.apply(x, idx, W1, Wv, bv, Wu, bu, w, b, Wc, bc, Wv2, bv2, Wu2, bu2, w2, b2, Wc2, bc2, label, G, S,
                          bool(return_cam))

@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from .. import _lib, ops
 from .._lib import F32
-from ..engine import Pool, _p, _stream, colsum, gemm, weight_grad
+from ..engine import Pool, _p, _stream, gemm
+from ..gated import gate_layer_bwd
 
 
 class _GatedPoolFn(torch.autograd.Function):
@@ -44,7 +45,6 @@ class _GatedPoolFn(torch.autograd.Function):
         D2, C = wvu.shape[0], wc.shape[0]
         D = D2 // 2
         dev = H.device
-        pool = Pool(dev)
         work = torch.empty(_lib.query("tm_attmil_bwd_workspace", N, L, D) // 4, device=dev)
         dZ, dH = torch.empty(N, D2, device=dev), torch.empty(N, L, device=dev)
         dM, dw, db = torch.empty(L, device=dev), torch.empty(1, D, device=dev), torch.empty(1, device=dev)
@@ -52,12 +52,7 @@ class _GatedPoolFn(torch.autograd.Function):
         _lib.call("tm_attmil_bwd", _p(Z), _p(H), _p(w.contiguous()), _p(p), _p(M), _p(wc.contiguous()),
                   _p(dlogits.float().contiguous()), N, L, D, C, _p(work), _p(dZ), _p(dH), _p(dM), _p(dw), _p(db),
                   _p(dwc), _p(dbc), _stream())
-        gemm(dZ, wvu.contiguous(), dH, N, L, D2, lda=D2, ldb=L, ldc=L, b_kn=1, dtype=F32, c_dtype=F32,
-             accumulate=True)
-        dwvu = torch.empty(D2, L, device=dev)
-        weight_grad(dZ, H, dwvu, D2, L, N, ldy=D2, ldx=L, dtype=F32, work_pool=pool)
-        dbvu = torch.empty(D2, device=dev)
-        colsum(dZ, N, D2, D2, F32, dbvu, pool)
+        dwvu, dbvu = gate_layer_bwd(dZ, H, wvu.contiguous(), dH, Pool(dev))
         return dH, dwvu, dbvu, dw, db, dwc, dbc
 
 

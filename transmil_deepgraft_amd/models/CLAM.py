@@ -21,28 +21,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from .._lib import F32
-from ..engine import Pool, _p, _stream, colsum, gemm, weight_grad
+from ..engine import Pool, _p, _stream
+from ..gated import _f32c, device_label, embed, embed_bwd
 
 IN_FEATURES = 1024
 MAX_CLASSES = 8
 MAX_K_SAMPLE = 32
-
-
-def _embed(x, W1, b1, Wab, bab):
-    """h [N, L] = ReLU(x W1^T + b1), Z [N, 2D] = h [Wa;Wb]^T + [ba;bb]."""
-    N, Fin = x.shape
-    L, D2 = W1.shape[0], Wab.shape[0]
-    h = torch.empty(N, L, device=x.device)
-    gemm(x, W1, h, N, L, Fin, lda=Fin, ldb=Fin, ldc=L, dtype=F32, c_dtype=F32)
-    _lib.call("tm_bias_act", F32, _p(h), _p(b1), N, L, 1, _stream())
-    Z = torch.empty(N, D2, device=x.device)
-    gemm(h, Wab, Z, N, D2, L, lda=L, ldb=L, ldc=D2, dtype=F32, c_dtype=F32, bias=bab)
-    return h, Z
-
-
-def _f32c(t):
-    return t.detach().float().contiguous()
 
 
 class _ClamFn(torch.autograd.Function):
@@ -59,7 +43,7 @@ class _ClamFn(torch.autograd.Function):
         W1_, b1_, Wc_, bc_, Wcls_, bcls_, Wic_, bic_ = (_f32c(t) for t in (W1, b1, Wc, bc, Wcls, bcls, Wic, bic))
         Wab = torch.cat([Wa.detach(), Wb.detach()]).float().contiguous()
         bab = torch.cat([ba.detach(), bb.detach()]).float().contiguous()
-        h, Z = _embed(x, W1_, b1_, Wab, bab)
+        h, Z = embed(x, W1_, b1_, Wab, bab)
         work = torch.empty(max(_lib.query("tm_clam_fwd_workspace", N, K), 4) // 4, device=dev)
         A_raw, stats = torch.empty(K, N, device=dev), torch.empty(K, 2, device=dev)
         M, logits = torch.empty(K, L, device=dev), torch.empty(1, K, device=dev)
@@ -85,11 +69,10 @@ class _ClamFn(torch.autograd.Function):
         if dlogits is None and (dloss is None or not ctx.inst):
             return (None,) * 16
         x, W1, Wab, Wc, Wcls, Wic, h, Z, A_raw, stats, M, idx, dil = ctx.saved_tensors
-        N, Fin = x.shape
+        N = x.shape[0]
         K, D, L = Wc.shape[0], Wc.shape[1], W1.shape[0]
         D2 = 2 * D
         dev = x.device
-        pool = Pool(dev)
         inst = ctx.inst and dloss is not None
         if dlogits is not None:
             dlogits = dlogits.float().contiguous()
@@ -105,22 +88,9 @@ class _ClamFn(torch.autograd.Function):
         _lib.call("tm_clam_bwd", _p(Z), _p(h), _p(A_raw), _p(stats), _p(M), N, L, D, K, _p(Wc), _p(Wcls), _p(Wic),
                   _p(idx if inst else None), _p(dil if inst else None), k, _p(dlogits), _p(dloss if inst else None),
                   _p(work), _p(dZ), _p(dh), _p(dWc), _p(dbc), _p(dWcls), _p(dbcls), _p(dWic), _p(dbic), _stream())
-        # attention_a / attention_b: dh += dZ [Wa;Wb], d[Wa;Wb] = dZ^T h, d[ba;bb] = colsum(dZ)
-        gemm(dZ, Wab, dh, N, L, D2, lda=D2, ldb=L, ldc=L, b_kn=1, dtype=F32, c_dtype=F32, accumulate=True)
-        dWab = torch.empty(D2, L, device=dev)
-        weight_grad(dZ, h, dWab, D2, L, N, ldy=D2, ldx=L, dtype=F32, work_pool=pool)
-        dbab = torch.empty(D2, device=dev)
-        colsum(dZ, N, D2, D2, F32, dbab, pool)
-        # the ReLU, then the first Linear
-        _lib.call("tm_clam_relu_bwd", _p(dh), _p(h), N * L, _stream())
-        dW1 = torch.empty(L, Fin, device=dev)
-        weight_grad(dh, x, dW1, L, Fin, N, ldy=L, ldx=Fin, dtype=F32, work_pool=pool)
-        db1 = torch.empty(L, device=dev)
-        colsum(dh, N, L, L, F32, db1, pool)
-        dx = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty(N, Fin, device=dev)
-            gemm(dh, W1, dx, N, Fin, L, lda=L, ldb=Fin, ldc=Fin, b_kn=1, dtype=F32, c_dtype=F32)
+        # attention_a / attention_b, the ReLU, then the first Linear
+        dx, dW1, db1, dWab, dbab = embed_bwd(dZ, dh, h, x, W1, Wab, Pool(dev), need_dx=ctx.needs_input_grad[0],
+                                             need_dW1=True, need_db1=True)
         return (dx, dW1, db1, dWab[:D], dbab[:D], dWab[D:], dbab[D:], dWc, dbc, dWcls, dbcls, dWic, dbic,
                 None, None, None)
 
@@ -152,9 +122,7 @@ def clam_pool(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wcls, bcls, Wic, bic, label=Non
         if x.shape[0] < k_sample:
             raise RuntimeError(f"CLAM_MB: selected index k out of range (a bag of {x.shape[0]} instances, "
                                f"k_sample = {k_sample})")
-        if not label.is_cuda or label.dtype != torch.int64:
-            raise RuntimeError("CLAM_MB: label must be an int64 GPU tensor (it is read on the device)")
-        label = label.reshape(-1)
+        label = device_label(label, "CLAM_MB")
     logits, loss, A_raw, M, idx, preds, targets = _ClamFn.apply(x, W1, b1, Wa, ba, Wb, bb, Wc, bc, Wcls, bcls, Wic,
                                                                 bic, label, k_sample, bool(subtyping))
     return logits, A_raw, M, loss, idx, preds, targets
@@ -164,7 +132,7 @@ def clam_scores(x, W1, b1, Wa, ba, Wb, bb, Wc, bc):
     """``A_raw [K, N]`` alone (``attention_only``): the two GEMMs and the score pass.  Not differentiable."""
     x = _check_input(x)
     with torch.no_grad():
-        h, Z = _embed(x, _f32c(W1), _f32c(b1), torch.cat([Wa, Wb]).float().contiguous(),
+        h, Z = embed(x, _f32c(W1), _f32c(b1), torch.cat([Wa, Wb]).float().contiguous(),
                       torch.cat([ba, bb]).float().contiguous())
         K, D = Wc.shape
         A_raw = torch.empty(K, x.shape[0], device=x.device)
