@@ -407,6 +407,27 @@ int tm_attmil_bwd(const float* Z, const float* H, const float* w, const float* p
                   const float* Wc, const float* dlogits, int N, int L, int D, int C, float* work,
                   float* dZ, float* dH, float* dM, float* dw, float* db, float* dWc, float* dbc, void* stream);
 
+/* The typed pooling: the same mathematics with Z [N, 2D], H [N, L] and dZ [N, 2D] stored as dtype
+ * (TM_F32 or TM_BF16: the model's bf16 compute mode); every other tensor and all arithmetic fp32.
+ * Forward (two launches: a row pass of tm_attmil_pool_rows_per_block() rows per workgroup, then the
+ * flash-style merge of its block partials) writes a [N], stats [2] = {max a, sum exp(a - max)}, M [L]
+ * and logits [C]; backward (three launches) recomputes p from a and stats and writes dZ (dtype),
+ * dH [N, L] = p dM (fp32; the caller's GEMM then adds dZ [Wv;Wu]), dw [D], db [1], dWc [C, L],
+ * dbc [C].  No float atomics: results repeat bitwise.  Refused before any device work: N < 1, L not
+ * a multiple of 8 or > 4096, D not a multiple of 8 or > 512, C outside [1, 256], a null pointer, or
+ * one of Z, H, w, a, M, Wc, work, dZ, dH, dw, dWc not 16-byte aligned.  work sized by the queries
+ * (0 for a refused shape). */
+int tm_attmil_pool_rows_per_block(void);
+long long tm_attmil_pool_fwd_workspace(int N, int L);
+int tm_attmil_pool_fwd(int dtype, const void* Z, const void* H, const float* w, const float* b,
+                       const float* Wc, const float* bc, int N, int L, int D, int C, float* work,
+                       float* a, float* stats, float* M, float* logits, void* stream);
+long long tm_attmil_pool_bwd_workspace(int N, int L, int D);
+int tm_attmil_pool_bwd(int dtype, const void* Z, const void* H, const float* w, const float* a,
+                       const float* stats, const float* M, const float* Wc, const float* dlogits,
+                       int N, int L, int D, int C, float* work, void* dZ, float* dH, float* dw,
+                       float* db, float* dWc, float* dbc, void* stream);
+
 /* ---- Chowder scores, two-sided top-R and head (chowder.hip) -- code/models/Chowder.py:19-50 ----
  * x [B, N, L] contiguous of dtype TM_F32 / TM_BF16 (all arithmetic fp32), w [L] / b [1] = the 1x1
  * Conv1d f1, W1 [H1, 2R] / b1, W2 [H2, H1] / b2, W3 [C, H2] / b3 = the three Linear layers of f2.
@@ -559,6 +580,9 @@ int tm_fc1_gelu_bwd(int dtype, const float* dH, const void* pre, int B, int N, i
 /* dpre = dy * GELU'(pre) elementwise (fp32 dy / pre, dpre in dtype): the backward of the inner
  * Linear + GELU of the in_features = 2048 _fc1 branch (code/models/TransMIL.py:100-111) */
 int tm_gelu_bwd(int dtype, const float* dy, const float* pre, long long count, void* dpre, void* stream);
+/* the same with pre and dpre both stored as dtype (the pre-activation a tm_gemm epilogue kept with
+ * pre_bf16); count % 8 == 0, 16-B aligned */
+int tm_gelu_bwd_pre(int dtype, const float* dy, const void* pre, long long count, void* dpre, void* stream);
 /* y = max(a + b, 0) elementwise (the C5 encoder's residual add + ReLU, Bottleneck.forward,
  * code/models/ResNet.py:97-124); 16-B aligned, y may alias a */
 int tm_add_relu(int dtype, const void* a, const void* b, void* y, long long count, void* stream);

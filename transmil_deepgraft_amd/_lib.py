@@ -148,6 +148,11 @@ _SIGS = {
     "tm_attmil_fwd": (I, [P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
     "tm_attmil_bwd_workspace": (L, [I, I, I]),
     "tm_attmil_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P, P]),
+    "tm_attmil_pool_rows_per_block": (I, []),
+    "tm_attmil_pool_fwd_workspace": (L, [I, I]),
+    "tm_attmil_pool_fwd": (I, [I, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P]),
+    "tm_attmil_pool_bwd_workspace": (L, [I, I, I]),
+    "tm_attmil_pool_bwd": (I, [I, P, P, P, P, P, P, P, P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "tm_chowder_fwd_workspace": (L, [I, I, I, I]),
     "tm_chowder_fwd": (I, [I, P, I, I, I, P, P, I, P, P, I, P, P, I, P, P, I, P, P, P, P, P, P, P]),
     "tm_chowder_bwd_workspace": (L, [I, I, I, I, I, I]),
@@ -197,6 +202,7 @@ _SIGS = {
     "tm_pad_rows": (I, [I, P, I, I, I, I, I, P, P]),
     "tm_fc1_gelu_bwd": (I, [I, P, P, I, I, I, I, I, P, P, P]),
     "tm_gelu_bwd": (I, [I, P, P, L, P, P]),
+    "tm_gelu_bwd_pre": (I, [I, P, P, L, P, P]),
     "tm_cast_f32_many": (I, [I, C.POINTER(CastTable), P]),
     "tm_eval_record": (I, [P, P, I, I, I, P, P, P, P, P, P, P, P]),
     "tm_eval_patients": (I, [P, P, P, P, I, I, I, I, P, P, P, P, P]),

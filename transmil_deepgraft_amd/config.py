@@ -89,7 +89,9 @@ def build_model(cfg, device="cuda"):
     """``models.{Model.name}(n_classes, in_features, out_features)`` on the device, in the compute
     dtype of ``General.precision``; wrapped in the RetCCL encoder for ``backbone: retccl``, in the
     ResNet-18 encoder for ``backbone: resnet18`` and in the MIL-AB tile CNN for ``backbone: simple``
-    on images (``Model.backbone == 'features'`` keeps feature bags)."""
+    on images (``Model.backbone == 'features'`` keeps feature bags).  The compute dtype is set on every
+    model that has ``set_compute_dtype``: TransMIL and its subclasses MDMIL / CTMIL, TransformerMIL and
+    AttMIL, whose ``precision: 16`` configs thereby run its bf16 mode (``models/AttMIL.py``)."""
     from . import models
     name = cfg.Model.name
     if not hasattr(models, name):

@@ -225,3 +225,311 @@ extern "C" int tm_attmil_bwd(const float* Z, const float* H, const float* w, con
   TM_CHECK_LAUNCH();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// The typed pooling (tm_attmil_pool_*): the same mathematics on Z / H / dZ rows stored as T = fp32
+// or bf16 (the model's bf16 compute mode), fp32 arithmetic and fp32 everything else, in clam.hip's
+// structure for its single-branch case.
+// Forward, two stream-ordered launches:
+//   pool_rows_fwd_kernel   PRB rows per workgroup.  A wave per row computes a_i from one read of the Z
+//                          row (16-byte loads); the workgroup then takes its own maximum m_blk and
+//                          s_blk = sum exp(a - m_blk) and adds exp(a - m_blk) H_i from one read of
+//                          each H row.
+//   pool_finalize_kernel   merges the block partials flash-style (m = max m_blk, each partial
+//                          weighted by exp(m_blk - m)): stats = {m, s}, M, logits.
+//   No exp of an unshifted score and no score-sized statistics pass.  a is saved; p is recomputed.
+// Backward, three launches:
+//   pool_bwd_head_kernel   dM = dl Wc, dWc = dl^T M, dbc = dl, r = M . dM (= sum_j p_j dp_j)
+//   pool_rows_bwd_kernel   p_i = exp(a_i - m) / s, dp_i = H_i . dM, da_i = p_i (dp_i - r), dZ through
+//                          tanh / sigmoid (stored as T), dH_i = p_i dM (fp32), block partials of dw / db
+//   pool_bwd_reduce_kernel dw, db = the block partials added in block order
+// No float atomics: every sum is a fixed tree or an index-ordered loop, so results repeat bitwise.
+namespace {
+
+constexpr int PRB = 64;           // rows per row-pass workgroup (tm_attmil_pool_rows_per_block)
+constexpr int POOL_LMAX = 4096;   // L: width of H
+constexpr int POOL_DMAX = 512;    // D: gate width (one 8-wide piece per lane of a wave)
+constexpr int POOL_CMAX = 256;    // classes
+constexpr int PFIN_THREADS = 1024;
+static_assert(PRB == 64, "the block statistics take one score per lane of wave 0");
+
+template <typename T>
+__global__ void __launch_bounds__(256) pool_rows_fwd_kernel(const T* __restrict__ Z, const T* __restrict__ H,
+                                                            const float* __restrict__ w, const float* __restrict__ b,
+                                                            int N, int L, int D, float* __restrict__ a,
+                                                            float* __restrict__ mb, float* __restrict__ sb,
+                                                            float* __restrict__ part) {
+  __shared__ float sc[PRB];                                        // scores, then exp(a - m_blk)
+  __shared__ __attribute__((aligned(16))) float comb[256 * 8];     // the row groups' partial sums
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  const int r0 = blockIdx.x * PRB, nrows = min(N - r0, PRB);
+  const float b0 = b[0];
+  for (int j = wv; j < nrows; j += 4) {
+    const T* z = Z + (size_t)(r0 + j) * 2 * D;
+    float acc = 0.f;
+    for (int d = 8 * lane; d < D; d += 512) {
+      f32x8 th, sg;
+      gate_parts8(load8f<T>(z + d), load8f<T>(z + D + d), th, sg);
+      acc = dot8(th * sg, load8f<float>(w + d), acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) {
+      sc[j] = acc + b0;
+      a[r0 + j] = acc + b0;
+    }
+  }
+  __syncthreads();
+  if (wv == 0) {
+    const float v = lane < nrows ? sc[lane] : -INFINITY;
+    const float m = wave_max(v);
+    const float e = lane < nrows ? expf(v - m) : 0.f;
+    const float s = wave_sum(e);
+    if (lane < nrows) sc[lane] = e;
+    if (lane == 0) {
+      mb[blockIdx.x] = m;
+      sb[blockIdx.x] = s;
+    }
+  }
+  __syncthreads();
+  // pooled partial: a thread owns one 8-column piece; with fewer than 256 pieces the rows are dealt
+  // over G = 256 / pieces groups, whose sums are then added in group order
+  const int nch = L / 8;
+  const T* hb = H + (size_t)r0 * L;
+  float* out = part + (size_t)blockIdx.x * L;
+  if (nch >= 256) {
+    for (int c = t; c < nch; c += 256) {
+      f32x8 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+      for (int j = 0; j < nrows; ++j) acc += sc[j] * load8f<T>(hb + (size_t)j * L + 8 * c);
+      store8<float>(out + 8 * c, acc);
+    }
+    return;
+  }
+  const int G = 256 / nch, g = t / nch, c = t - g * nch;
+  f32x8 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (g < G) {
+#pragma unroll 4
+    for (int j = g; j < nrows; j += G) acc += sc[j] * load8f<T>(hb + (size_t)j * L + 8 * c);
+    if (g > 0) store8<float>(comb + (size_t)(g * nch + c) * 8, acc);        // (g * nch + c) < 256
+  }
+  __syncthreads();
+  if (g == 0) {
+    for (int q = 1; q < G; ++q) acc += load8f<float>(comb + (size_t)(q * nch + c) * 8);
+    store8<float>(out + 8 * c, acc);
+  }
+}
+
+// One workgroup.  Slice q of the column groups adds the blocks q, q + S, ... in order; the S slices
+// are then added in order.
+__global__ void __launch_bounds__(PFIN_THREADS) pool_finalize_kernel(
+    const float* __restrict__ mb, const float* __restrict__ sb, const float* __restrict__ part, int nblk, int L,
+    const float* __restrict__ Wc, const float* __restrict__ bc, int C, float* __restrict__ stats,
+    float* __restrict__ M, float* __restrict__ logits) {
+  __shared__ __attribute__((aligned(16))) float acc_s[POOL_LMAX];   // [S][L], S * L <= 4096
+  __shared__ float Ms[POOL_LMAX];
+  __shared__ float red[PFIN_THREADS / 64];
+  const int t = threadIdx.x;
+  float m = -INFINITY;
+  for (int k = t; k < nblk; k += PFIN_THREADS) m = fmaxf(m, mb[k]);
+  m = block_reduce<true, PFIN_THREADS / 64>(m, red);
+  float s = 0.f;
+  for (int k = t; k < nblk; k += PFIN_THREADS) s += sb[k] * expf(mb[k] - m);
+  s = block_reduce<false, PFIN_THREADS / 64>(s, red);
+  const int ncg = L / 4, S = PFIN_THREADS / ncg, slice = t / ncg, col = (t - slice * ncg) * 4;
+  if (slice < S) {
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = slice; k < nblk; k += S) acc += expf(mb[k] - m) * *(const f32x4*)(part + (size_t)k * L + col);
+    *(f32x4*)(acc_s + slice * L + col) = acc;
+  }
+  __syncthreads();
+  for (int c = t; c < L; c += PFIN_THREADS) {
+    float v = acc_s[c];
+    for (int q = 1; q < S; ++q) v += acc_s[q * L + c];
+    v /= s;
+    M[c] = v;
+    Ms[c] = v;
+  }
+  __syncthreads();
+  const int wv = t >> 6, lane = t & 63;
+  for (int k = wv; k < C; k += PFIN_THREADS / 64) {          // a wave per class
+    float acc = 0.f;
+    for (int c = lane; c < L; c += 64) acc = fmaf(Ms[c], Wc[(size_t)k * L + c], acc);
+    acc = wave_sum(acc);
+    if (lane == 0) logits[k] = acc + bc[k];
+  }
+  if (t == 0) {
+    stats[0] = m;
+    stats[1] = s;
+  }
+}
+
+__global__ void __launch_bounds__(256) pool_bwd_head_kernel(const float* __restrict__ dl, const float* __restrict__ M,
+                                                            const float* __restrict__ Wc, int C, int L,
+                                                            float* __restrict__ dM, float* __restrict__ rv,
+                                                            float* __restrict__ dWc, float* __restrict__ dbc) {
+  __shared__ float red[4];
+  float racc = 0.f;
+  for (int c = threadIdx.x; c < L; c += 256) {
+    const float mc = M[c];
+    float s = 0.f;
+    for (int k = 0; k < C; ++k) {
+      s = fmaf(dl[k], Wc[(size_t)k * L + c], s);
+      dWc[(size_t)k * L + c] = dl[k] * mc;
+    }
+    dM[c] = s;
+    racc = fmaf(mc, s, racc);
+  }
+  const float r = block_reduce<false, 4>(racc, red);
+  if (threadIdx.x == 0) rv[0] = r;
+  for (int k = threadIdx.x; k < C; k += 256) dbc[k] = dl[k];
+}
+
+// PRB rows per workgroup, a wave per row.  LDS: dMs [L] | buf [4][D] | dbs [4]
+template <typename T>
+__global__ void __launch_bounds__(256) pool_rows_bwd_kernel(
+    const T* __restrict__ Z, const T* __restrict__ H, const float* __restrict__ w, const float* __restrict__ a,
+    const float* __restrict__ stats, const float* __restrict__ dM, const float* __restrict__ rv, int N, int L, int D,
+    T* __restrict__ dZ, float* __restrict__ dH, float* __restrict__ dw_part, float* __restrict__ db_part) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  float* dMs = sm;
+  float* buf = dMs + L;
+  float* dbs = buf + 4 * D;
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  for (int e = t; e < L; e += 256) dMs[e] = dM[e];
+  __syncthreads();
+  const float m = stats[0], inv = 1.f / stats[1], r = rv[0];
+  const int r0 = blockIdx.x * PRB, r1 = min(N, r0 + PRB);
+  const int d = 8 * lane;                                  // D <= 512: one 8-wide piece per lane
+  f32x8 dwacc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, wd = dwacc;
+  if (d < D) wd = load8f<float>(w + d);
+  float dbacc = 0.f;
+#pragma unroll 1
+  for (int i = r0 + wv; i < r1; i += 4) {
+    const T* h = H + (size_t)i * L;
+    float dp = 0.f;
+    for (int c = 8 * lane; c < L; c += 512) dp = dot8(load8f<T>(h + c), load8f<float>(dMs + c), dp);
+    dp = wave_sum(dp);
+    const float p = expf(a[i] - m) * inv, da = p * (dp - r);
+    dbacc += da;
+    float* gh = dH + (size_t)i * L;
+    for (int c = 8 * lane; c < L; c += 512) store8<float>(gh + c, p * load8f<float>(dMs + c));
+    if (d < D) {
+      const T* z = Z + (size_t)i * 2 * D;
+      T* gz = dZ + (size_t)i * 2 * D;
+      f32x8 th, sg, ga, gb;
+      gate_parts8(load8f<T>(z + d), load8f<T>(z + D + d), th, sg);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        dwacc[u] = fmaf(da, th[u] * sg[u], dwacc[u]);
+        const GateGrad gg = gate_bwd(da * wd[u], th[u], sg[u]);
+        ga[u] = gg.a;
+        gb[u] = gg.b;
+      }
+      store8f<T>(gz + d, ga);
+      store8f<T>(gz + D + d, gb);
+    }
+  }
+  // the four waves' dw / db partials, added in wave order
+  if (d < D) store8<float>(buf + wv * D + d, dwacc);
+  if (lane == 0) dbs[wv] = dbacc;
+  __syncthreads();
+  for (int e = t; e < D; e += 256)
+    dw_part[(size_t)blockIdx.x * D + e] = buf[e] + buf[D + e] + buf[2 * D + e] + buf[3 * D + e];
+  if (t == 0) db_part[blockIdx.x] = dbs[0] + dbs[1] + dbs[2] + dbs[3];
+}
+
+// dw[e] / db = the block partials added in block order
+__global__ void __launch_bounds__(256) pool_bwd_reduce_kernel(const float* __restrict__ dw_part,
+                                                              const float* __restrict__ db_part, int nblk, int D,
+                                                              float* __restrict__ dw, float* __restrict__ db) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < D) {
+    float s = 0.f;
+    for (int k = 0; k < nblk; ++k) s += dw_part[(size_t)k * D + e];
+    dw[e] = s;
+  } else if (e == D) {
+    float s = 0.f;
+    for (int k = 0; k < nblk; ++k) s += db_part[k];
+    db[0] = s;
+  }
+}
+
+int pool_nblk(int N) { return (N + PRB - 1) / PRB; }
+
+const char* pool_check_shape(int dtype, int N, int L, int D, int C) {
+  if (dtype != TM_F32 && dtype != TM_BF16) return "attmil_pool: dtype must be TM_F32 or TM_BF16";
+  if (N < 1) return "attmil_pool: N must be >= 1";
+  if (L < 8 || L % 8 != 0 || L > POOL_LMAX) return "attmil_pool: L must be a multiple of 8, <= 4096";
+  if (D < 8 || D % 8 != 0 || D > POOL_DMAX) return "attmil_pool: D must be a multiple of 8, <= 512";
+  if (C < 1 || C > POOL_CMAX) return "attmil_pool: C must be in [1, 256]";
+  return nullptr;
+}
+
+bool pool_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+}  // namespace
+
+extern "C" int tm_attmil_pool_rows_per_block(void) { return PRB; }
+
+extern "C" long long tm_attmil_pool_fwd_workspace(int N, int L) {
+  if (N < 1 || L < 8 || L % 8 != 0 || L > POOL_LMAX) return 0;
+  return (long long)pool_nblk(N) * (L + 2) * (long long)sizeof(float);
+}
+
+extern "C" int tm_attmil_pool_fwd(int dtype, const void* Z, const void* H, const float* w, const float* b,
+                                  const float* Wc, const float* bc, int N, int L, int D, int C, float* work, float* a,
+                                  float* stats, float* M, float* logits, void* stream) {
+  const char* bad = pool_check_shape(dtype, N, L, D, C);
+  TM_REQUIRE(bad == nullptr, bad);
+  TM_REQUIRE(Z && H && w && b && Wc && bc && work && a && stats && M && logits, "attmil_pool_fwd: null pointer");
+  TM_REQUIRE(pool_al16(Z) && pool_al16(H) && pool_al16(w) && pool_al16(Wc) && pool_al16(work) && pool_al16(a) &&
+                 pool_al16(M),
+             "attmil_pool_fwd: Z, H, w, Wc, work, a and M must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = pool_nblk(N);
+  float* part = work;                          // [nblk][L], 16-B aligned rows
+  float* mb = part + (size_t)nblk * L;         // [nblk]
+  float* sb = mb + nblk;                       // [nblk]
+  if (dtype == TM_BF16)
+    pool_rows_fwd_kernel<bf16><<<nblk, 256, 0, st>>>((const bf16*)Z, (const bf16*)H, w, b, N, L, D, a, mb, sb, part);
+  else
+    pool_rows_fwd_kernel<float><<<nblk, 256, 0, st>>>((const float*)Z, (const float*)H, w, b, N, L, D, a, mb, sb, part);
+  pool_finalize_kernel<<<1, PFIN_THREADS, 0, st>>>(mb, sb, part, nblk, L, Wc, bc, C, stats, M, logits);
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" long long tm_attmil_pool_bwd_workspace(int N, int L, int D) {
+  if (N < 1 || L < 8 || L % 8 != 0 || L > POOL_LMAX || D < 8 || D % 8 != 0 || D > POOL_DMAX) return 0;
+  return ((long long)L + 4 + (long long)pool_nblk(N) * (D + 1)) * (long long)sizeof(float);
+}
+
+extern "C" int tm_attmil_pool_bwd(int dtype, const void* Z, const void* H, const float* w, const float* a,
+                                  const float* stats, const float* M, const float* Wc, const float* dlogits, int N,
+                                  int L, int D, int C, float* work, void* dZ, float* dH, float* dw, float* db,
+                                  float* dWc, float* dbc, void* stream) {
+  const char* bad = pool_check_shape(dtype, N, L, D, C);
+  TM_REQUIRE(bad == nullptr, bad);
+  TM_REQUIRE(Z && H && w && a && stats && M && Wc && dlogits && work && dZ && dH && dw && db && dWc && dbc,
+             "attmil_pool_bwd: null pointer");
+  TM_REQUIRE(pool_al16(Z) && pool_al16(H) && pool_al16(w) && pool_al16(a) && pool_al16(M) && pool_al16(Wc) &&
+                 pool_al16(work) && pool_al16(dZ) && pool_al16(dH) && pool_al16(dw) && pool_al16(dWc),
+             "attmil_pool_bwd: Z, H, w, a, M, Wc, work, dZ, dH, dw and dWc must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const int nblk = pool_nblk(N);
+  float* dM = work;                            // [L]
+  float* rv = dM + L;                          // [4]: r = M . dM
+  float* dw_part = rv + 4;                     // [nblk][D]
+  float* db_part = dw_part + (size_t)nblk * D; // [nblk]
+  pool_bwd_head_kernel<<<1, 256, 0, st>>>(dlogits, M, Wc, C, L, dM, rv, dWc, dbc);
+  const size_t lds = ((size_t)L + 4 * (size_t)D + 4) * sizeof(float);      // <= 24.1 KiB
+  if (dtype == TM_BF16)
+    pool_rows_bwd_kernel<bf16><<<nblk, 256, lds, st>>>((const bf16*)Z, (const bf16*)H, w, a, stats, dM, rv, N, L, D,
+                                                       (bf16*)dZ, dH, dw_part, db_part);
+  else
+    pool_rows_bwd_kernel<float><<<nblk, 256, lds, st>>>((const float*)Z, (const float*)H, w, a, stats, dM, rv, N, L, D,
+                                                        (float*)dZ, dH, dw_part, db_part);
+  pool_bwd_reduce_kernel<<<(D + 1 + 255) / 256, 256, 0, st>>>(dw_part, db_part, nblk, D, dw, db);
+  TM_CHECK_LAUNCH();
+  return 0;
+}

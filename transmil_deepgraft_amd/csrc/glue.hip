@@ -182,6 +182,20 @@ __global__ void gelu_bwd_kernel(const float* __restrict__ dy, const float* __res
   }
 }
 
+// the same with the pre-activation stored in T (tm_gemm_args.pre_bf16), 8 elements per thread
+template <typename T>
+__global__ __launch_bounds__(256) void gelu_bwd_pre_kernel(const float* __restrict__ dy, const T* __restrict__ pre,
+                                                           size_t count, T* __restrict__ dpre) {
+  const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  if (i >= count) return;
+  const f32x8 g = load8<float>(dy + i);
+  const vec8<T> x = load8<T>(pre + i);
+  vec8<T> out;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) out[e] = from_f<T>(g[e] * gelu_erf_grad(to_f(x[e])));
+  store8<T>(dpre + i, out);
+}
+
 // y[b][pad + i][c] = x[b*S + i][c] (cast to T), y[b][0..pad)[c] = 0; grid (n_pad, B)
 template <typename T>
 __global__ void pad_rows_kernel(const float* __restrict__ x, int S, int n_pad, int pad, int D, T* __restrict__ y) {
@@ -365,6 +379,19 @@ extern "C" int tm_gelu_bwd(int dtype, const float* dy, const float* pre, long lo
   const unsigned blocks = (unsigned)(((count + 3) / 4 + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
   TM_DTYPE_DISPATCH(dtype, (gelu_bwd_kernel<T><<<blocks, 256, 0, st>>>(dy, pre, (size_t)count, (T*)dpre)));
+  TM_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int tm_gelu_bwd_pre(int dtype, const float* dy, const void* pre, long long count, void* dpre,
+                               void* stream) {
+  TM_REQUIRE(dy && pre && dpre && count >= 0 && count % 8 == 0, "gelu_bwd_pre: count must be a multiple of 8");
+  TM_REQUIRE(((uintptr_t)dy % 16) == 0 && ((uintptr_t)pre % 16) == 0 && ((uintptr_t)dpre % 16) == 0,
+             "gelu_bwd_pre: dy / pre / dpre must be 16-B aligned");
+  if (count == 0) return 0;
+  const unsigned blocks = (unsigned)((count / 8 + 255) / 256);
+  hipStream_t st = (hipStream_t)stream;
+  TM_DTYPE_DISPATCH(dtype, (gelu_bwd_pre_kernel<T><<<blocks, 256, 0, st>>>(dy, (const T*)pre, (size_t)count, (T*)dpre)));
   TM_CHECK_LAUNCH();
   return 0;
 }

@@ -59,6 +59,37 @@ TM_DEV GateGrad gate_bwd(float dg, float th, float sg) {
   return {dg * sg * (1.f - th * th), dg * th * sg * (1.f - sg)};
 }
 
+// Typed rows (T = float or bf16 storage, fp32 arithmetic): 8 consecutive elements of a row as
+// floats and back (bf16: one 16-byte access; fp32: two).  p must be 16-B aligned.
+template <typename T>
+TM_DEV f32x8 load8f(const T* p) {
+  const vec8<T> v = load8<T>(p);
+  f32x8 r;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) r[e] = to_f(v[e]);
+  return r;
+}
+template <typename T>
+TM_DEV void store8f(T* p, const f32x8& x) {
+  vec8<T> v;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = from_f<T>(x[e]);
+  store8<T>(p, v);
+}
+TM_DEV float dot8(const f32x8& a, const f32x8& b, float acc) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) acc = fmaf(a[u], b[u], acc);
+  return acc;
+}
+// th = tanh(za), sg = sigmoid(zb) of 8 gate inputs; the gate itself is th * sg
+TM_DEV void gate_parts8(const f32x8& za, const f32x8& zb, f32x8& th, f32x8& sg) {
+#pragma unroll
+  for (int u = 0; u < 8; ++u) {
+    th[u] = tanhf(za[u]);
+    sg[u] = sigmoid_(zb[u]);
+  }
+}
+
 // Two-sided selection: (score, instance index) pairs in ascending-score order (before_min) and in
 // descending-score order (before_max); among equal scores the lower index comes first in both.
 struct Pair {

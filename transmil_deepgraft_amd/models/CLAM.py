@@ -8,7 +8,7 @@ Same constructor, submodule layout and parameter names, so the reference's state
 bag logits from one read of Z and h; the per-class two-sided top-``k_sample`` selection and the
 instance classifiers' cross entropy with the label read on the device).  The backward is
 ``tm_clam_bwd`` plus the GEMM / column-sum launches of the three Linear layers and one ReLU-backward
-pass.  fp32 throughout, like AttMIL's pooling (there is no ``set_compute_dtype``).
+pass.  fp32 throughout, like AttMIL's fp32 mode (there is no ``set_compute_dtype``).
 
 The reference ranks the softmaxed attention; the kernels rank the raw fp32 scores (the softmax is
 monotone) and, among equal scores, take the lower instance index first (torch leaves that order

@@ -5,7 +5,9 @@ submodules.  These ops back the module-by-module path it then takes (and
 ``TransLayer.forward`` / ``PPEG.forward`` / the norms when a caller drives a submodule
 on its own): the reference's GradCAM / attention visualisation hooks ``model.norm`` and
 ``model.layer{1,2}.norm`` (code/visualize_mil.py:225-234, test_visualize.py:122,127).
-fp32 operands throughout (a visualisation / analysis path, not the benchmark step).
+fp32 operands throughout (a visualisation / analysis path, not the benchmark step), except the
+``*_bf16`` variants at the end of the file (``models/AttMIL.py``'s bf16 compute mode), which no other
+caller reaches.
 """
 from __future__ import annotations
 
@@ -295,3 +297,85 @@ def attention(qkv, heads, scale, compute_dtype=torch.float32):
     if compute_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"attention: compute_dtype must be float32 or bfloat16, got {compute_dtype}")
     return _AttentionFn.apply(qkv.float(), heads, float(scale), BF16 if compute_dtype == torch.bfloat16 else F32)
+
+
+# ----------------------------------------------------------------------------- bf16 operand variants
+def cast_bf16_many(srcs, dsts=None):
+    """bf16 copies of up to 8 fp32 tensors (GEMM weight operands) in ONE ``tm_cast_f32_many`` launch.
+    ``dsts``: preallocated bf16 destinations (contiguous; a view into a larger buffer stacks several
+    weights without a concatenation), default fresh tensors.  Element counts must be multiples of 4."""
+    srcs = [s.detach().contiguous() for s in srcs]
+    if dsts is None:
+        dsts = [torch.empty(s.shape, dtype=torch.bfloat16, device=s.device) for s in srcs]
+    tab = _lib.CastTable()
+    tab.count = len(srcs)
+    off = 0
+    for i, (s, d) in enumerate(zip(srcs, dsts)):
+        if s.dtype != torch.float32 or d.dtype != torch.bfloat16 or d.numel() != s.numel() or not d.is_contiguous():
+            raise ValueError("cast_bf16_many: fp32 sources and contiguous bf16 destinations of the same size")
+        tab.src[i], tab.dst[i], tab.offset[i] = s.data_ptr(), d.data_ptr(), off
+        off += s.numel()
+    tab.offset[len(srcs)] = off
+    _lib.call("tm_cast_f32_many", BF16, C.byref(tab), _stream())
+    return dsts
+
+
+def as_bf16_rows(x):
+    """A bag [..., K] as a contiguous bf16 [M, K] GEMM operand: a bf16 bag is read as it is (no fp32
+    copy), anything else is cast once (``tm_cast_f32``)."""
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.dtype == torch.bfloat16:
+        return x2.contiguous()
+    x2 = x2.float().contiguous()
+    out = torch.empty(x2.shape, dtype=torch.bfloat16, device=x2.device)
+    _lib.call("tm_cast_f32", BF16, _p(x2), _p(out), x2.numel(), _stream())
+    return out
+
+
+class _LinearGeluBf16Fn(torch.autograd.Function):
+    """y = GELU(x W^T + b) with bf16 operands and fp32 accumulation: y fp32, the pre-activation kept
+    in bf16 (``pre_bf16``, the TransMIL 2048 branch's treatment).  ``wt``: the bf16 copy of ``w``.
+    Backward: dpre (bf16) = dy GELU'(pre), dX = dpre W, dW = dpre^T X and db in fp32."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, wt):
+        shp = x.shape
+        K = shp[-1]
+        x2 = as_bf16_rows(x)
+        M, Nout = x2.shape[0], w.shape[0]
+        y = torch.empty(M, Nout, device=x.device)
+        pre = torch.empty(M, Nout, dtype=torch.bfloat16, device=x.device)
+        gemm(x2, wt, y, M, Nout, K, lda=K, ldb=K, ldc=Nout, dtype=BF16, c_dtype=F32, bias=b, gelu=True, pre=pre,
+             ld_pre=Nout, pre_bf16=True)
+        ctx.save_for_backward(x2, wt, pre)
+        ctx.shp = shp
+        return y.view(*shp[:-1], Nout)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, wt, pre = ctx.saved_tensors
+        M, K = x2.shape
+        Nout = wt.shape[0]
+        pool = Pool(dy.device)
+        dpre = torch.empty(M, Nout, dtype=torch.bfloat16, device=dy.device)
+        _lib.call("tm_gelu_bwd_pre", BF16, _p(dy.float().reshape(M, Nout).contiguous()), _p(pre), M * Nout, _p(dpre),
+                  _stream())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(M, K, device=dy.device)
+            gemm(dpre, wt, dx, M, K, Nout, lda=Nout, ldb=K, ldc=K, b_kn=1, dtype=BF16, c_dtype=F32)
+            dx = dx.view(ctx.shp)
+        dw = torch.empty(Nout, K, device=dy.device)
+        db = torch.empty(Nout, device=dy.device)
+        weight_grad(dpre, x2, dw, Nout, K, M, ldy=Nout, ldx=K, dtype=BF16, work_pool=pool, bias_out=db)
+        return dx, dw, db, None
+
+
+def linear_gelu_bf16(lin, x, wt):
+    """``linear_gelu`` with bf16 operands (``wt``: the bf16 copy of ``lin.weight``, see
+    ``cast_bf16_many``): x [..., K] bf16 (read as it is) or fp32 (cast once) -> fp32 [..., Nout]."""
+    if not x.is_cuda:
+        raise RuntimeError("HIP Linear+GELU needs a GPU tensor")
+    if lin.out_features % 8 or lin.in_features % 8:
+        raise ValueError("linear_gelu_bf16: feature counts must be multiples of 8")
+    return _LinearGeluBf16Fn.apply(x, lin.weight, lin.bias, wt)
