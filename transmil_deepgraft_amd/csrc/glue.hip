@@ -323,6 +323,7 @@ __global__ void __launch_bounds__(256) ce_bwd_kernel(const float* __restrict__ p
 extern "C" int tm_ce_fwd(const float* logits, const long long* label, int B, int C, float* loss, float* prob,
                          long long* yhat, int* class_stats, void* stream) {
   TM_REQUIRE(B >= 1 && C >= 1, "ce_fwd: empty logits");
+  TM_REQUIRE(logits && label && loss && prob && yhat, "ce_fwd: null arg");   // class_stats may be null
   ce_fwd_kernel<<<1, 256, 0, (hipStream_t)stream>>>(logits, label, B, C, loss, prob, yhat, class_stats);
   TM_CHECK_LAUNCH();
   return 0;
@@ -330,12 +331,16 @@ extern "C" int tm_ce_fwd(const float* logits, const long long* label, int B, int
 
 extern "C" int tm_ce_bwd(const float* prob, const long long* label, int B, int C, const float* g, float* dlogits,
                          void* stream) {
+  TM_REQUIRE(B >= 1 && C >= 1, "ce_bwd: empty logits");
+  TM_REQUIRE(prob && label && g && dlogits, "ce_bwd: null arg");
   ce_bwd_kernel<<<(B * C + 255) / 256, 256, 0, (hipStream_t)stream>>>(prob, label, B, C, g, dlogits);
   TM_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int tm_put_cls(const float* cls, int B, int S, int D, float* H, void* stream) {
+  TM_REQUIRE(B >= 1 && S >= 1 && D >= 1, "put_cls: bad shape");
+  TM_REQUIRE(cls && H, "put_cls: null arg");
   put_cls_kernel<<<B, 256, 0, (hipStream_t)stream>>>(cls, S, D, H);
   TM_CHECK_LAUNCH();
   return 0;

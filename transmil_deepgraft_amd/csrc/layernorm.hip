@@ -38,6 +38,16 @@ TM_DEV void load_row_t(float (&v)[VPL], const T* p, int lane) {
   }
 }
 
+// a * b rounded to fp32, never contracted into an add or subtract that consumes it.  The row mean
+// of ln_fwd_kernel: the rows are centred on the value that mean_out stores (the backward recomputes
+// x^ from it).  Left to fp contraction, the compiler fused the product into `v - mean` in some
+// instantiations only (bf16 output at D = 384), which then centred on the unrounded sum / D: a
+// constant row came out as beta + O(1e-5) there and as beta exactly at the other widths.
+TM_DEV float mul_rounded(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
 // rows: B*S input rows (fp32 residual stream); out row = (r / S) * n_pad + pad + r % S
 template <typename T, int VPL>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
@@ -64,7 +74,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) s += v[i];
-  const float mean = wave_sum(s) * (1.0f / D);
+  const float mean = mul_rounded(wave_sum(s), 1.0f / D);
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) { const float d = v[i] - mean; q += d * d; }
@@ -222,84 +232,15 @@ __global__ void head_bwd_kernel(const float* __restrict__ dlogits, int B, int C,
                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                 const float* __restrict__ W, float* __restrict__ dW, float* __restrict__ dbias,
                                 float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dh) {
-  constexpr int D = VPL * 64;
   const int lane = threadIdx.x;
-  if (B == 1 && C <= 4) {
-    // one bag (the reference's batch size), few classes: every load first, one memory round trip
-    float dl[4], gm[VPL], bt[VPL], xh[VPL], w[4][VPL];
+  if (B == 1 && C <= 4) {   // one bag (the reference's batch size), few classes
+    float dl[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) dl[k] = k < C ? dlogits[k] : 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      gm[i] = gamma[c]; bt[i] = beta[c]; xh[i] = xhat[c];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) w[k][i] = k < C ? W[(size_t)k * D + c] : 0.f;
-    }
-    float g[VPL], s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      float dy = 0.f;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (k < C) {
-          dW[(size_t)k * D + c] = 0.f + dl[k] * (xh[i] * gm[i] + bt[i]);
-          dy += dl[k] * w[k][i];
-        }
-      dgamma[c] = 0.f + dy * xh[i];
-      dbeta[c] = 0.f + dy;
-      g[i] = dy * gm[i];
-      s1 += g[i];
-      s2 += g[i] * xh[i];
-    }
-    if (lane == 0)
-      for (int k = 0; k < C; ++k) dbias[k] = 0.f + dl[k];
-    s1 = wave_sum(s1) * (1.0f / D);
-    s2 = wave_sum(s2) * (1.0f / D);
-    const float rs = rstd[0];
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) dh[lane * VPL + i] = rs * (g[i] - s1 - xh[i] * s2);
+    head_bwd_b1_dl<VPL>(dl, C, xhat, rstd, gamma, beta, W, dW, dbias, dgamma, dbeta, dh, nullptr, lane);
     return;
   }
-  float dgm[VPL], dbt[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) { dgm[i] = 0.f; dbt[i] = 0.f; }
-  for (int k = 0; k < C; ++k) {
-    float s = 0.f;
-    for (int b = 0; b < B; ++b) s += dlogits[b * C + k];
-    if (lane == 0) dbias[k] = s;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      float acc = 0.f;
-      for (int b = 0; b < B; ++b) acc += dlogits[b * C + k] * (xhat[(size_t)b * D + c] * gamma[c] + beta[c]);
-      dW[(size_t)k * D + c] = acc;
-    }
-  }
-  for (int b = 0; b < B; ++b) {
-    float g[VPL], xh[VPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      float dy = 0.f;
-      for (int k = 0; k < C; ++k) dy += dlogits[b * C + k] * W[(size_t)k * D + c];
-      xh[i] = xhat[(size_t)b * D + c];
-      dgm[i] += dy * xh[i];
-      dbt[i] += dy;
-      g[i] = dy * gamma[c];
-      s1 += g[i];
-      s2 += g[i] * xh[i];
-    }
-    s1 = wave_sum(s1) * (1.0f / D);
-    s2 = wave_sum(s2) * (1.0f / D);
-    const float rs = rstd[b];
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) dh[(size_t)b * S * D + lane * VPL + i] = rs * (g[i] - s1 - xh[i] * s2);
-  }
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) { dgamma[lane * VPL + i] = dgm[i]; dbeta[lane * VPL + i] = dbt[i]; }
+  head_bwd_general<VPL>(dlogits, B, C, S, xhat, rstd, gamma, beta, W, dW, dbias, dgamma, dbeta, dh, lane);
 }
 
 // Head + loss of the training step in ONE launch (the step's tail was four latency-bound launches:
@@ -392,7 +333,6 @@ __global__ void head_ce_bwd_kernel(const float* __restrict__ prob, const long lo
                                    const float* __restrict__ W, float* __restrict__ dW, float* __restrict__ dbias,
                                    float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dh,
                                    float* __restrict__ dl_scratch) {
-  constexpr int D = VPL * 64;
   const int lane = threadIdx.x;
   const float gs = g[0] / (float)B;
   if (B == 1 && C <= 4) {
@@ -406,49 +346,12 @@ __global__ void head_ce_bwd_kernel(const float* __restrict__ prob, const long lo
     dl_scratch[i] = gs * (prob[i] - (c == (int)label[b] ? 1.f : 0.f)) + (dlogits_in ? dlogits_in[i] : 0.f);
   }
   __syncthreads();
-  const float* dlogits = dl_scratch;
-  float dgm[VPL], dbt[VPL];
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) { dgm[i] = 0.f; dbt[i] = 0.f; }
-  for (int k = 0; k < C; ++k) {
-    float s = 0.f;
-    for (int b = 0; b < B; ++b) s += dlogits[b * C + k];
-    if (lane == 0) dbias[k] = s;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      float acc = 0.f;
-      for (int b = 0; b < B; ++b) acc += dlogits[b * C + k] * (xhat[(size_t)b * D + c] * gamma[c] + beta[c]);
-      dW[(size_t)k * D + c] = acc;
-    }
-  }
-  for (int b = 0; b < B; ++b) {
-    float gg[VPL], xh[VPL];
-    float s1 = 0.f, s2 = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-      const int c = lane * VPL + i;
-      float dy = 0.f;
-      for (int k = 0; k < C; ++k) dy += dlogits[b * C + k] * W[(size_t)k * D + c];
-      xh[i] = xhat[(size_t)b * D + c];
-      dgm[i] += dy * xh[i];
-      dbt[i] += dy;
-      gg[i] = dy * gamma[c];
-      s1 += gg[i];
-      s2 += gg[i] * xh[i];
-    }
-    s1 = wave_sum(s1) * (1.0f / D);
-    s2 = wave_sum(s2) * (1.0f / D);
-    const float rs = rstd[b];
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) dh[(size_t)b * S * D + lane * VPL + i] = rs * (gg[i] - s1 - xh[i] * s2);
-  }
-#pragma unroll
-  for (int i = 0; i < VPL; ++i) { dgamma[lane * VPL + i] = dgm[i]; dbeta[lane * VPL + i] = dbt[i]; }
+  head_bwd_general<VPL>(dl_scratch, B, C, S, xhat, rstd, gamma, beta, W, dW, dbias, dgamma, dbeta, dh, lane);
 }
 
 }  // namespace
 
+#define TM_BAD_WIDTH "layernorm: D must be 64/128/256/384/512/768/1024"
 #define TM_VPL_DISPATCH(D, CALL)                        \
   switch (D) {                                          \
     case 64: { constexpr int VPL = 1; CALL; break; }    \
@@ -458,12 +361,19 @@ __global__ void head_ce_bwd_kernel(const float* __restrict__ prob, const long lo
     case 512: { constexpr int VPL = 8; CALL; break; }   \
     case 768: { constexpr int VPL = 12; CALL; break; }  \
     case 1024: { constexpr int VPL = 16; CALL; break; } \
-    default: tm_set_error("layernorm: D must be 64/128/256/384/512/768/1024"); return 1; \
+    default: tm_set_error(TM_BAD_WIDTH); return 1; \
   }
+
+// the shape checks come before the pointer checks: a refused shape is reported as such whatever
+// the pointers are (the status-path tests pass none)
+#define TM_REQUIRE_WIDTH(D)                                                                          \
+  TM_REQUIRE((D) == 64 || (D) == 128 || (D) == 256 || (D) == 384 || (D) == 512 || (D) == 768 || (D) == 1024, \
+             TM_BAD_WIDTH)
 
 extern "C" int tm_layernorm_fwd(const float* x, const float* gamma, const float* beta, float eps, int rows, int D,
                                 int S, int n_pad, int pad, int dtype, void* y, float* mean, float* rstd,
                                 void* stream) {
+  TM_REQUIRE_WIDTH(D);
   TM_REQUIRE(x && gamma && beta && y && mean && rstd && S > 0 && rows % S == 0, "layernorm_fwd: bad args");
   TM_REQUIRE(n_pad >= S + pad, "layernorm_fwd: n_pad < S + pad");
   const int total = rows + (rows / S) * pad;
@@ -488,8 +398,12 @@ extern "C" int tm_layernorm_bwd(const void* dy, int dtype, const float* x, const
                                 const float* rstd, int rows, int D, int S, int n_pad, int pad, int rows_per_block,
                                 int resid_cls_only, float* dx_accum, float* work, float* dgamma, float* dbeta,
                                 tm_reduce_queue* rq, void* stream) {
-  TM_REQUIRE(dy && x && gamma && mean && rstd && dx_accum && work && dgamma && dbeta, "layernorm_bwd: null arg");
+  TM_REQUIRE_WIDTH(D);
   TM_REQUIRE(rows_per_block > 0 && S > 0, "layernorm_bwd: bad args");
+  // dy is read at row (r / S) * n_pad + pad + r % S for every r < rows
+  TM_REQUIRE(rows % S == 0, "layernorm_bwd: rows must be a multiple of S");
+  TM_REQUIRE(pad >= 0 && n_pad >= S + pad, "layernorm_bwd: n_pad < S + pad");
+  TM_REQUIRE(dy && x && gamma && mean && rstd && dx_accum && work && dgamma && dbeta, "layernorm_bwd: null arg");
   const int nb = (rows + rows_per_block - 1) / rows_per_block;
   hipStream_t st = (hipStream_t)stream;
   if (dtype == TM_BF16) {
@@ -510,11 +424,14 @@ extern "C" int tm_layernorm_bwd_seg(const void* dy, int dtype, const float* x, c
                                     int resid_cls_only, const float* seg_add, int seg_len, int nseg, int seg_rows,
                                     float* dx_accum, float* work, float* dgamma, float* dbeta, tm_reduce_queue* rq,
                                     void* stream) {
+  TM_REQUIRE_WIDTH(D);
+  TM_REQUIRE(rows_per_block > 0 && S > 0 && seg_len > 0 && nseg >= 0 && seg_rows > nseg, "layernorm_bwd_seg: bad args");
+  TM_REQUIRE(rows % S == 0, "layernorm_bwd_seg: rows must be a multiple of S");
+  TM_REQUIRE(pad >= 0 && n_pad >= S + pad, "layernorm_bwd_seg: n_pad < S + pad");
+  TM_REQUIRE((long long)(pad + S - 1) / seg_len < nseg, "layernorm_bwd_seg: rows past the segments");
+  TM_REQUIRE(dtype == TM_BF16, "layernorm_bwd_seg: bf16 dy only");
   TM_REQUIRE(dy && x && gamma && mean && rstd && dx_accum && work && dgamma && dbeta && seg_add,
              "layernorm_bwd_seg: null arg");
-  TM_REQUIRE(rows_per_block > 0 && S > 0 && seg_len > 0 && nseg >= 0 && seg_rows > nseg, "layernorm_bwd_seg: bad args");
-  TM_REQUIRE((long long)(pad + S - 1) / seg_len < nseg && pad + S <= n_pad, "layernorm_bwd_seg: rows past the segments");
-  TM_REQUIRE(dtype == TM_BF16, "layernorm_bwd_seg: bf16 dy only");
   const int nb = (rows + rows_per_block - 1) / rows_per_block;
   hipStream_t st = (hipStream_t)stream;
   const SegAdd sg{seg_add, seg_len, nseg, seg_rows};
@@ -530,6 +447,8 @@ extern "C" int tm_layernorm_bwd_seg(const void* dy, int dtype, const float* x, c
 extern "C" int tm_head_fwd(const float* h, int B, int S, int D, const float* gamma, const float* beta, float eps,
                            const float* W, const float* bias, int C, float* logits, float* xhat, float* rstd,
                            void* stream) {
+  TM_REQUIRE_WIDTH(D);
+  TM_REQUIRE(S >= 1, "head_fwd: S must be at least 1");
   TM_REQUIRE(h && gamma && beta && W && bias && logits && xhat && rstd && B > 0 && C > 0, "head_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
   TM_VPL_DISPATCH(D, (head_fwd_kernel<VPL><<<B, 64, 0, st>>>(h, S, gamma, beta, eps, W, bias, C, logits, xhat, rstd)));
@@ -541,6 +460,8 @@ extern "C" int tm_head_ce_fwd(const float* h, int B, int S, int D, const float* 
                               const float* W, const float* bias, int C, const long long* label, float* logits,
                               float* xhat, float* rstd, float* loss, float* prob, long long* yhat, int* class_stats,
                               void* stream) {
+  TM_REQUIRE_WIDTH(D);
+  TM_REQUIRE(S >= 1, "head_ce_fwd: S must be at least 1");
   TM_REQUIRE(h && gamma && beta && W && bias && label && logits && xhat && rstd && loss && prob && yhat && B > 0 &&
                  C > 0, "head_ce_fwd: bad args");
   hipStream_t st = (hipStream_t)stream;
@@ -555,6 +476,9 @@ extern "C" int tm_head_ce_bwd(const float* prob, const long long* label, const f
                               int B, int C, int S, int D, const float* xhat, const float* rstd, const float* gamma,
                               const float* beta, const float* W, float* dW, float* dbias, float* dgamma, float* dbeta,
                               float* dh, float* scratch, void* stream) {
+  TM_REQUIRE_WIDTH(D);
+  TM_REQUIRE(S >= 1, "head_ce_bwd: S must be at least 1");
+  TM_REQUIRE(B >= 1 && C >= 1, "head_ce_bwd: empty logits");
   TM_REQUIRE(prob && label && gloss && xhat && rstd && gamma && beta && W && dW && dbias && dgamma && dbeta && dh,
              "head_ce_bwd: null arg");
   TM_REQUIRE((B == 1 && C <= 4) || scratch, "head_ce_bwd: scratch [B*C] needed unless B == 1 and C <= 4");
@@ -569,6 +493,9 @@ extern "C" int tm_head_ce_bwd(const float* prob, const long long* label, const f
 extern "C" int tm_head_bwd(const float* dlogits, int B, int C, int S, int D, const float* xhat, const float* rstd,
                            const float* gamma, const float* beta, const float* W, float* dW, float* dbias,
                            float* dgamma, float* dbeta, float* dh, void* stream) {
+  TM_REQUIRE_WIDTH(D);
+  TM_REQUIRE(S >= 1, "head_bwd: S must be at least 1");
+  TM_REQUIRE(B >= 1 && C >= 1, "head_bwd: empty logits");
   TM_REQUIRE(dlogits && xhat && rstd && gamma && beta && W && dW && dbias && dgamma && dbeta && dh,
              "head_bwd: null arg");
   hipStream_t st = (hipStream_t)stream;
