@@ -381,11 +381,16 @@ int tm_split_f32(const float* x, void* y, long long count, void* stream);
  * wfold [49][D] tap-major (the three depthwise kernels + identity folded into one 7x7), bfold [D] */
 int tm_ppeg_fold(const float* w7, const float* b7, const float* w5, const float* b5, const float* w3,
                  const float* b3, int D, float* wfold, float* bfold, void* stream);
+/* x, y [B, 1 + G*G, D] fp32, D % 32 == 0; y must not alias x; x, y, wfold, bfold 16-byte aligned */
 int tm_ppeg_fwd(const float* x, int B, int G, int D, const float* wfold, const float* bfold, float* y,
                 void* stream);
 long long tm_ppeg_bwd_workspace(int B, int G, int D);
-/* dout (nullable): also writes the padded to_out-dropout gradient of the TransLayer below from dx
- * (as tm_dropout_bwd_pad with the same dtype / n_pad / pad / p / seed / seed_ptr).  The weight
+/* dx (=) must alias neither dy nor x (the weight-gradient blocks read x while the stencil blocks of
+ * the same launch write dx); x, dy, dx, wfold, work and dout 16-byte aligned; work and the six
+ * gradients are required.
+ * dout (nullable): also writes the padded to_out-dropout gradient of the TransLayer below from dx
+ * (as tm_dropout_bwd_pad with the same dtype / n_pad / pad / p / seed / seed_ptr: rows [0, pad)
+ * zero, rows pad + S .. n_pad - 1 left alone).  The weight
  * gradients (=) are summed from the workspace's slabs by tm_splitk_reduce: deferred into rq when
  * it is non-null (final after tm_reduce_flush), else summed before return */
 int tm_ppeg_bwd(const float* x, const float* dy, int B, int G, int D, const float* wfold, float* dx,
@@ -569,9 +574,13 @@ int tm_ce_fwd(const float* logits, const long long* label, int B, int C, float* 
               long long* yhat, int* class_stats, void* stream);
 int tm_ce_bwd(const float* prob, const long long* label, int B, int C, const float* g, float* dlogits,
               void* stream);
+/* out [B, n_pad, D] T, n_pad >= pad + S: rows [0, pad) of a bag zero, row pad + i =
+ * T(keep(b*S + i, c) / (1 - p) * dH[b*S + i][c]) for i < S; rows pad + S .. n_pad - 1 have no input
+ * row and are left alone (as tm_layernorm_fwd and the fused store of tm_ppeg_bwd leave them) */
 int tm_dropout_bwd_pad(int dtype, const float* dH, int B, int S, int n_pad, int pad, int D, float p,
                        uint64_t seed, const uint64_t* seed_ptr, void* out, void* stream);
-/* NystromAttention eq. 1 for a raw input: [B*S, D] fp32 -> front-padded [B, n_pad, D] T */
+/* NystromAttention eq. 1 for a raw input: [B*S, D] fp32 -> front-padded [B, n_pad, D] T (rows
+ * [0, pad) zero, rows pad + S .. n_pad - 1 left alone) */
 int tm_pad_rows(int dtype, const float* x, int B, int S, int n_pad, int pad, int D, void* y, void* stream);
 /* _fc1 GELU backward + grid-pad fold: dpre (dtype T) = (dH[token] + dH[dup]) * GELU'(pre); `pre` is the
  * forward's pre-activation in the same T (fp32 for TM_F32, bf16 for TM_BF16: tm_gemm_args.pre_bf16) */

@@ -402,6 +402,37 @@ def test_dropout_mask_is_one_function_of_seed_row_column(S, n, pad, use_ptr):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_dropout_bwd_pad_and_pad_rows_leave_the_tail_rows_alone(dtype):
+    """(B, S, n_pad, pad, D) = (2, 7, 16, 5, 64), p = 0.7: four rows per bag past pad + S, which have
+    no input row.  The input holds exactly B * S rows and the outputs one extra row, prefilled with 7.
+    Data and pad rows as in test_dropout_mask_is_one_function_of_seed_row_column (bitwise); the tail
+    rows and the extra row keep the sentinel.  Both kernels used to launch n_pad rows per bag and
+    filled the tail from the next bag's rows (past the input, for the last bag)."""
+    L = _lib()
+    _p, _stream = _eng()
+    B, S, n, pad, D, p = 2, 7, 16, 5, 64, 0.7
+    sp, ctr = _seed_args(True)
+    keep = torch.from_numpy(R.dropout_keep(ctr, SEED, B * S, D, p))
+    dH = torch.randn(B * S, D, generator=torch.Generator(device="cpu").manual_seed(S))
+    dHd = dH.to(DEV)
+    scale = torch.tensor(float(R.drop_scale_f32(p)))
+    out = torch.full((B * n + 1, D), SENTINEL, dtype=dtype, device=DEV)
+    L.call("tm_dropout_bwd_pad", _tt(dtype), _p(dHd), B, S, n, pad, D, C.c_float(p), C.c_uint64(SEED), _p(sp), _p(out),
+           _stream())
+    y = torch.full((B * n + 1, D), SENTINEL, dtype=dtype, device=DEV)
+    L.call("tm_pad_rows", _tt(dtype), _p(dHd), B, S, n, pad, D, _p(y), _stream())
+    torch.cuda.synchronize()
+    want = torch.full((B * n + 1, D), SENTINEL)
+    want_y = want.clone()
+    want[:-1].view(B, n, D)[:, :pad] = 0.0
+    want[:-1].view(B, n, D)[:, pad:pad + S] = torch.where(keep, dH * scale, torch.zeros(())).view(B, S, D)
+    want_y[:-1].view(B, n, D)[:, :pad] = 0.0
+    want_y[:-1].view(B, n, D)[:, pad:pad + S] = dH.view(B, S, D)
+    assert torch.equal(out.cpu(), want.to(dtype))
+    assert torch.equal(y.cpu(), want_y.to(dtype))
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("p", [0.0, 0.7])
 @pytest.mark.parametrize("use_ptr", [False, True])
 @pytest.mark.parametrize("S,n,pad", DROP_SHAPES)

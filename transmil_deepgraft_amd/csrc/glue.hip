@@ -108,7 +108,7 @@ __global__ void put_cls_kernel(const float* __restrict__ cls, int S, int D, floa
 }
 
 // out[b][pad + i][c] = dH[b*S + i][c] * keep(b*S+i, c) * scale ; out[b][0..pad)[c] = 0
-// grid (n_pad, B), block 256
+// grid (pad + S, B), block 256: rows pad + S .. n_pad - 1 of a bag have no input row and are left alone
 template <typename T>
 __global__ void dropout_bwd_pad_kernel(const float* __restrict__ dH, int S, int n_pad, int pad, int D, float p,
                                        float scale, uint64_t seed0, const uint64_t* __restrict__ seed_ptr,
@@ -196,7 +196,8 @@ __global__ __launch_bounds__(256) void gelu_bwd_pre_kernel(const float* __restri
   store8<T>(dpre + i, out);
 }
 
-// y[b][pad + i][c] = x[b*S + i][c] (cast to T), y[b][0..pad)[c] = 0; grid (n_pad, B)
+// y[b][pad + i][c] = x[b*S + i][c] (cast to T), y[b][0..pad)[c] = 0; grid (pad + S, B): rows
+// pad + S .. n_pad - 1 of a bag are left alone
 template <typename T>
 __global__ void pad_rows_kernel(const float* __restrict__ x, int S, int n_pad, int pad, int D, T* __restrict__ y) {
   const int t = blockIdx.x, b = blockIdx.y, i = t - pad;
@@ -350,7 +351,9 @@ extern "C" int tm_dropout_bwd_pad(int dtype, const float* dH, int B, int S, int 
                                   uint64_t seed, const uint64_t* seed_ptr, void* out, void* stream) {
   TM_REQUIRE(n_pad >= S + pad, "dropout_bwd_pad: n_pad < S + pad");
   const float scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
-  TM_DTYPE_DISPATCH(dtype, (dropout_bwd_pad_kernel<T><<<dim3(n_pad, B), 256, 0, (hipStream_t)stream>>>(
+  // one block per row that has an input row or is a pad row: the tail rows pad + S .. would read
+  // dH past the bag (past the buffer, for the last bag)
+  TM_DTYPE_DISPATCH(dtype, (dropout_bwd_pad_kernel<T><<<dim3(pad + S, B), 256, 0, (hipStream_t)stream>>>(
                                dH, S, n_pad, pad, D, p, scale, seed, seed_ptr, (T*)out)));
   TM_CHECK_LAUNCH();
   return 0;
@@ -359,7 +362,7 @@ extern "C" int tm_dropout_bwd_pad(int dtype, const float* dH, int B, int S, int 
 extern "C" int tm_pad_rows(int dtype, const float* x, int B, int S, int n_pad, int pad, int D, void* y,
                            void* stream) {
   TM_REQUIRE(n_pad >= S + pad, "pad_rows: n_pad < S + pad");
-  TM_DTYPE_DISPATCH(dtype, (pad_rows_kernel<T><<<dim3(n_pad, B), 256, 0, (hipStream_t)stream>>>(
+  TM_DTYPE_DISPATCH(dtype, (pad_rows_kernel<T><<<dim3(pad + S, B), 256, 0, (hipStream_t)stream>>>(
                                x, S, n_pad, pad, D, (T*)y)));
   TM_CHECK_LAUNCH();
   return 0;

@@ -42,7 +42,8 @@ constexpr int WIN = WR * WC;                                       // 196 cells
 
 // Backward only, optional: the next layer-backward's first step fused into the stencil's stores --
 // dout[b][pad + t][c] = T(keep(b*S + t, c) * scale * dx[b*S + t][c]) and zero pad rows, the
-// padded to_out-dropout gradient of the TransLayer below (as tm_dropout_bwd_pad).
+// padded to_out-dropout gradient of the TransLayer below (as tm_dropout_bwd_pad; rows pad + S .. of
+// a bag are left alone).
 struct DropPad {
   void* out;        // null: off
   int dtype, n_pad, pad;
@@ -304,19 +305,25 @@ extern "C" int tm_ppeg_fold(const float* w7, const float* b7, const float* w5, c
   return 0;
 }
 
-// x, y: [B, S, D] fp32 with S = 1 + G*G.  y must not alias x.
 static int wgrad_groups(int G) {
   const int ntc = (G + TC - 1) / TC;
   return ((G + TR - 1) / TR) * ((ntc + WT - 1) / WT);
 }
 
+// the kernels move 16-B pieces (f32x4 / buffer loads) from and to these
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 // x, y: [B, S, D] fp32 with S = 1 + G*G.  y must not alias x.
 extern "C" int tm_ppeg_fwd(const float* x, int B, int G, int D, const float* wfold, const float* bfold, float* y,
                            void* stream) {
-  TM_REQUIRE(x && y && x != y && D % CW == 0 && G > 0 && B > 0, "ppeg_fwd: bad args");
+  TM_REQUIRE(D > 0 && D % CW == 0 && G > 0 && B > 0, "ppeg_fwd: bad shape");
   // the tile kernels address one bag's grid through a buffer resource with 32-bit byte counts /
   // offsets: beyond 4 GiB per bag the hardware bounds check would turn loads into silent zeros
   TM_REQUIRE((1LL + (long long)G * G) * D * 4 < (1LL << 32), "ppeg_fwd: (1+G*G)*D*4 must be < 2^32 bytes per bag");
+  TM_REQUIRE(x && y && wfold && bfold, "ppeg_fwd: null arg");
+  TM_REQUIRE(x != y, "ppeg_fwd: y must not alias x");
+  TM_REQUIRE(aligned16(x) && aligned16(y) && aligned16(wfold) && aligned16(bfold),
+             "ppeg_fwd: x, y, wfold, bfold must be 16-byte aligned");
   const int ntiles = ((G + TR - 1) / TR) * ((G + TC - 1) / TC);
   ppeg_stencil_kernel<false><<<dim3(ntiles * (D / CW), B), 256, ST_LDS, (hipStream_t)stream>>>(
       x, 1 + G * G, G, D, wfold, bfold, y, DropPad{});
@@ -328,15 +335,23 @@ extern "C" long long tm_ppeg_bwd_workspace(int B, int G, int D) {
   return (long long)B * wgrad_groups(G) * D * (NT + 25 + 9 + 1) * (long long)sizeof(float);
 }
 
-// dy: [B,S,D] upstream gradient; x: PPEG input.  dx written (=); weight grads written.
+// dy: [B,S,D] upstream gradient; x: PPEG input.  dx written (=); weight grads written.  dx must
+// alias neither dy nor x: the stencil blocks write dx while the stencil blocks of other tiles read
+// dy and the weight-gradient blocks of the same launch read x.  dout (nullable) [B, n_pad, D] T:
+// rows [0, pad) zero, rows [pad, pad + S) from dx, rows pad + S .. left alone.
 extern "C" int tm_ppeg_bwd(const float* x, const float* dy, int B, int G, int D, const float* wfold, float* dx,
                            float* work, float* dw7, float* db7, float* dw5, float* db5, float* dw3, float* db3,
                            int dtype, void* dout, int n_pad, int pad, float p, uint64_t seed,
                            const uint64_t* seed_ptr, tm_reduce_queue* rq, void* stream) {
-  TM_REQUIRE(x && dy && dx && dx != dy && D % CW == 0 && G > 0 && B > 0, "ppeg_bwd: bad args");
+  TM_REQUIRE(D > 0 && D % CW == 0 && G > 0 && B > 0, "ppeg_bwd: bad shape");
   TM_REQUIRE((1LL + (long long)G * G) * D * 4 < (1LL << 32), "ppeg_bwd: (1+G*G)*D*4 must be < 2^32 bytes per bag");
   TM_REQUIRE(!dout || ((dtype == TM_BF16 || dtype == TM_F32) && n_pad >= pad + 1 + G * G && pad >= 0),
              "ppeg_bwd: bad dropout-pad output");
+  TM_REQUIRE(x && dy && dx && wfold && work, "ppeg_bwd: null arg");
+  TM_REQUIRE(dw7 && db7 && dw5 && db5 && dw3 && db3, "ppeg_bwd: null gradient");
+  TM_REQUIRE(dx != dy && dx != x, "ppeg_bwd: dx must alias neither dy nor x");
+  TM_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(dx) && aligned16(wfold) && aligned16(work) && aligned16(dout),
+             "ppeg_bwd: x, dy, dx, wfold, work, dout must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const int S = 1 + G * G;
   const DropPad dp{dout, dtype, n_pad, pad, p, p > 0.f ? 1.f / (1.f - p) : 1.f, seed, seed_ptr};
