@@ -288,7 +288,7 @@ def test_cls_a1_row_fwd_bwd(B, n, r, dtype):
 # ============================================================================= c. class-row chain
 @pytest.mark.parametrize("B,n,r", [(1, 256, 254), (2, 1024, 5)])
 def test_cls_row_chain_into_fused_a3_and_assemble_q(B, n, r):
-    """The bf16 class-row path of engine.nystrom_core_backward: the dv window and dq row of
+    """The bf16 class-row path of engine.nystrom_core_backward (_core_backward_bf16): the dv window and dq row of
     tm_cls_a1_row_bwd (NaN everywhere else, as the pool's uninitialised buffers may be) feed
     tm_nys_a3_bwd_fused(dv_lo, dv_hi, dql = NULL) and tm_nys_assemble_q_slab(dq_row = r).  The
     whole dqkv (prefilled with NaN) is finite and each third within 2e-2 of the fp64 chain

@@ -13,6 +13,11 @@ Buffers:
     H*  [B*S, D] fp32 residual stream;  xn [B, n, D] T (LN output, pad rows 0)
     qkv [3, B*8, n, 64] T;  merged [B, n, D] T
 ``T`` is bf16 (bench mode) or fp32 (parity mode).
+
+The NystromAttention core is three straight-line pipelines behind ``nystrom_core_forward`` /
+``_backward``, chosen in one place (``core_mode``): the bf16 step (``_core_*_bf16``), the fp32 parity
+step (``_core_*_f32``) and the fp32 ``_nysg_core_*`` family for a geometry other than (64, 256).  The
+class-row layer's branches live inside the first two; tests/test_engine_trace_cpu.py pins every launch.
 """
 from __future__ import annotations
 
@@ -33,6 +38,7 @@ LN_EPS = 1e-5
 # (dim_head, landmarks) the HIP core runs: 512-wide on the MFMA kernels (both compute modes), the
 # 256- and 384-wide TransMIL geometries on the fp32 tm_nysg_* family (nystrom_geo.hip)
 GEOMETRIES = ((DH, NL), (32, 128), (48, 192))
+CORE_BF16, CORE_F32, CORE_GENERIC = "bf16", "f32", "generic"    # the core's three pipelines (core_mode)
 QROWS = NL + 32  # rows per bag of tm_cls_q_rows' operands (landmarks, class row, zero rows to 32 | rows)
 # bf16 class-row layer: the q part of to_qkv's backward as two small products (False: the dense q
 # block of dqkv; the equivalence test sets it)
@@ -121,11 +127,17 @@ class Geometry:
     heads: int
     dh: int = DH     # dim_head
     nl: int = NL     # landmarks
+    S: int = 0       # tokens per bag; 0: the grid-padded bag plus its class token
+
+    @classmethod
+    def for_sequence(cls, B, S, D, heads, dh=DH, nl=NL):
+        """A bare sequence of S D-wide tokens (standalone NystromAttention): no grid pad, no class token."""
+        return cls(B, max(S - 1, 1), D, D, heads, dh, nl, S=S)
 
     def __post_init__(self):
         self.G = int(math.ceil(math.sqrt(self.N)))
         self.add = self.G * self.G - self.N
-        self.S = self.G * self.G + 1
+        self.S = self.S or self.G * self.G + 1
         self.n = ((self.S + self.nl - 1) // self.nl) * self.nl
         self.pad = self.n - self.S
         self.l = self.n // self.nl
@@ -135,36 +147,34 @@ class Geometry:
 # ----------------------------------------------------------------------------- GEMM helpers
 def gemm(A, B, Cout, M, N, K, *, lda, ldb, ldc, a_trans=0, b_kn=0, dtype=BF16, c_dtype=None,
          alpha=1.0, bias=None, gelu=False, pre=None, ld_pre=0, drop_p=0.0, seed=0, seed_ptr=None, resid=None,
-         accumulate=False, rowmap=None, qkv=None, splits=1, k_per_split=None, pre_bf16=False):
+         accumulate=False, rowmap=None, qkv=None, splits=1, k_per_split=None, pre_bf16=False, splitk=False,
+         slab_bf16=False, colsum=None):
+    """One tm_gemm launch; the only place a GemmArgs is filled.  ``splitk``: Cout is the [splits, M, N] slab of
+    raw split partials (``slab_bf16``: stored bf16), no epilogue; ``colsum`` [splits, M]: also A's column sums."""
     g = GemmArgs()
     g.M, g.N, g.K = M, N, K
     g.lda, g.ldb, g.ldc = lda, ldb, ldc
     g.a_trans, g.b_kn = a_trans, b_kn
-    g.ab_dtype = dtype
-    g.c_dtype = dtype if c_dtype is None else c_dtype
-    g.splits = splits
+    g.ab_dtype, g.c_dtype = dtype, dtype if c_dtype is None else c_dtype
     bk = 64 if dtype == BF16 else 32
     if k_per_split is None:
         k_per_split = ((K + splits - 1) // splits + bk - 1) // bk * bk
-    g.k_per_split = max(k_per_split, 1)
-    g.mode = EPI_PLAIN
-    g.alpha = alpha
-    g.bias = _p(bias)
-    g.gelu = int(gelu)
-    g.pre = _p(pre)
-    g.ld_pre = ld_pre
-    g.pre_bf16 = int(pre_bf16)
-    g.drop_p = drop_p
-    g.drop_scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
-    g.seed = seed
-    g.seed_ptr = _p(seed_ptr)
-    g.resid = _p(resid)
-    g.accumulate = int(accumulate)
+    g.splits, g.k_per_split = splits, max(k_per_split, 1)
+    g.mode, g.alpha, g.accumulate = EPI_PLAIN, alpha, int(accumulate)
+    g.bias, g.gelu, g.resid = _p(bias), int(gelu), _p(resid)
+    g.pre, g.ld_pre, g.pre_bf16 = _p(pre), ld_pre, int(pre_bf16)
+    g.drop_p, g.seed, g.seed_ptr = drop_p, seed, _p(seed_ptr)
+    if not splitk:      # (the split-K epilogue applies no dropout: its scale stays 0)
+        g.drop_scale = 1.0 / (1.0 - drop_p) if drop_p > 0 else 1.0
     if rowmap is not None:
         g.grp_in, g.skip, g.grp_out, g.out_off, g.dup_n, g.dup_off = rowmap
     if qkv is not None:
         g.mode = EPI_QKV
         g.nbags, g.nh, g.dh, g.seq, g.qscale = qkv
+    if splitk:
+        g.mode = EPI_SPLITK
+        g.slab_bf16 = int(slab_bf16)
+        g.colsum = _p(colsum)
     _lib.call("tm_gemm", _p(A), _p(B), _p(Cout), C.byref(g), _stream())
 
 
@@ -205,20 +215,10 @@ def weight_grad(dY, X, out, M, N, K, *, ldy, ldx, dtype, work_pool, bias_out=Non
     # bf16 mode: bf16 split slabs (each split's partial rounded once, summed in fp32 by the flush)
     sb16 = dtype == BF16 if slab_bf16 is None else bool(slab_bf16) and dtype == BF16
     slab = work_pool(splits * M * N, torch.bfloat16) if sb16 else work_pool(splits * M * N)
-    g = GemmArgs()
-    g.M, g.N, g.K = M, N, K
-    g.lda, g.ldb, g.ldc = ldy, ldx, N
-    g.a_trans, g.b_kn = 1, 1
-    g.ab_dtype, g.c_dtype = dtype, F32
-    g.splits, g.k_per_split = splits, kps
-    g.mode = EPI_SPLITK
-    g.alpha = 1.0
-    g.slab_bf16 = int(sb16)
     fuse = bias_out is not None and dtype == BF16 and K % 64 == 0 and M % 8 == 0 and N % 8 == 0
     cs = work_pool(splits * M) if fuse else None
-    if fuse:
-        g.colsum = cs.data_ptr()
-    _lib.call("tm_gemm", _p(dY), _p(X), _p(slab), C.byref(g), _stream())
+    gemm(dY, X, slab, M, N, K, lda=ldy, ldb=ldx, ldc=N, a_trans=1, b_kn=1, dtype=dtype, c_dtype=F32, splits=splits,
+         k_per_split=kps, splitk=True, slab_bf16=sb16, colsum=cs)
     _lib.call("tm_splitk_reduce_bf16" if sb16 else "tm_splitk_reduce", _p(slab), _p(out), splits, M * N,
               C.c_float(1.0), 0, _rq(), _stream())
     if fuse:
@@ -397,73 +397,24 @@ class gemm_pair:
 
 
 # ----------------------------------------------------------------------------- NystromAttention core
+def core_mode(geo: Geometry, dt_code):
+    """The pipeline the core runs, decided here only.  (64, 256): the bf16 MFMA step or the fp32 MFMA
+    parity step, by compute mode; any other geometry: the fp32 tm_nysg_* family in both compute modes."""
+    if (geo.dh, geo.nl) != (DH, NL):
+        return CORE_GENERIC
+    return CORE_BF16 if dt_code == BF16 else CORE_F32
+
+
 def nystrom_core_forward(qkv, geo: Geometry, wconv, tdtype, dt_code, pool, cls_row=None):
     """App. A eq. 4-9 on q, k, v [3, B*h, n, 64] -> merged [B, n, h*64] (T) + saved state.
     ``cls_row``: only that row of merged (and of the A1 log-sum-exp) is computed (clsrow.hip).
-    A geometry other than (64, 256) runs the fp32 tm_nysg_* family: q, k, v and merged are fp32
-    in both compute modes (``_nysg_core_forward``)."""
-    if (geo.dh, geo.nl) != (DH, NL):
+    A geometry other than (64, 256): q, k, v and merged are fp32 in both compute modes (``_nysg_core_forward``)."""
+    mode = core_mode(geo, dt_code)
+    if mode == CORE_GENERIC:
         if cls_row is not None:
             raise NotImplementedError("the class-row layer runs at dim_head=64, num_landmarks=256 only")
         return _nysg_core_forward(qkv, geo, wconv, pool)
-    n, nbh, nh = geo.n, geo.nbh, geo.heads
-    q, k, v = qkv[0], qkv[1], qkv[2]
-    st = _stream()
-    ql = pool(nbh * NL * DH).view(nbh, NL, DH)
-    kl = pool(nbh * NL * DH).view(nbh, NL, DH)
-    ql_t = pool(nbh * NL * DH, tdtype).view(nbh, NL, DH)
-    kl_t = pool(nbh * NL * DH, tdtype).view(nbh, NL, DH)
-    with probe("landmarks"):
-        _lib.call("tm_nys_landmarks", dt_code, _p(q), _p(k), nbh, n, _p(ql), _p(kl), _p(ql_t), _p(kl_t), st)
-    a2 = pool(nbh * NL * NL).view(nbh, NL, NL)
-    w = pool(nbh * NL * DH).view(nbh, NL, DH)
-    lse3 = pool(nbh * NL)
-    work = pool(_lib.query("tm_nys_a3_workspace", nbh, n) // 4)
-    # (measured: running A3 V on a second stream beside the pseudo-inverse chain slowed
-    #  the step -- the chain's launches then wait for CUs -- so the path stays serial; in bench
-    #  mode the partials' combine runs inside the chain's last launch, on the CUs it leaves idle)
-    prec = 1 if dt_code == BF16 else 0
-    a2s = None
-    if prec:
-        # bench mode: the key-split A3 forward also writes A2 (+ its split bf16 hi/lo planes, the
-        # operands of the pseudo-inverse chain, pinv_split.hip); the partials' combine runs in the
-        # chain's last launch
-        a2s = pool(nbh * NL * NL)   # hi + lo bf16 planes = one fp32 matrix's bytes
-        with probe("a3_fwd"):
-            _lib.call("tm_nys_a3_fwd_sim2", _p(ql), _p(kl), _p(k), _p(v), nbh, n, _p(work), _p(a2), _p(a2s), st)
-    else:
-        with probe("a3_fwd"):
-            _lib.call("tm_nys_a3_fwd", dt_code, _p(ql), _p(k), _p(v), nbh, n, _p(work), _p(w), _p(lse3), st)
-    if prec:
-        saved = pool(_lib.query("tm_pinv_split_saved_floats", nbh, PINV_ITERS))
-        with probe("pinv_fwd"):
-            _lib.call("tm_pinv_fwd_split_a3", _p(a2), _p(a2s), nbh, PINV_ITERS, _p(saved), _p(work),
-                      _lib.query("tm_nys_a3_partials", nbh, n), _p(w), _p(lse3), st)
-        z = saved[:nbh * NL * NL].view(nbh, NL, NL)
-    else:
-        saved = pool(_lib.query("tm_pinv_saved_floats", nbh, PINV_ITERS))
-        _lib.call("tm_nys_sim2_softmax", _p(ql), _p(kl), nbh, _p(a2), st)
-        _lib.call("tm_pinv_fwd", _p(a2), nbh, PINV_ITERS, prec, _p(saved), st)
-        z = saved[PINV_ITERS * nbh * NL * NL:(PINV_ITERS + 1) * nbh * NL * NL].view(nbh, NL, NL)
-    y = pool(nbh * NL * DH).view(nbh, NL, DH)
-    if dt_code == BF16:     # Y and its bf16 operand copy from the same launch
-        y_t = pool(nbh * NL * DH, tdtype)
-        bmm([bmm_job(z, 0, w, 0, y, NL, DH, NL, Ct=y_t, ct_mode=1)], nbh, prec)
-    else:
-        bmm([bmm_job(z, 0, w, 0, y, NL, DH, NL)], nbh, prec)
-        y_t = y
-    merged = pool(geo.B * n * nh * DH, tdtype).view(geo.B, n, nh * DH)
-    lse1 = pool(nbh * n)
-    if cls_row is not None:
-        _lib.call("tm_cls_a1_row_fwd", dt_code, _p(q), _p(v), _p(kl_t), _p(y_t), _p(wconv), nbh, nh, n, cls_row,
-                  _p(merged), _p(lse1), st)
-    else:
-        with probe("a1_fwd"):
-            _lib.call("tm_nys_a1_fwd", dt_code, _p(q), _p(v), _p(kl_t), _p(y_t), _p(wconv), nbh, nh, n, _p(merged),
-                      _p(lse1), st)
-    state = dict(ql=ql, kl=kl, ql_t=ql_t, kl_t=kl_t, a2=a2, a2s=a2s, pinv=saved, z=z, w=w, lse3=lse3, y=y,
-                 y_t=y_t, lse1=lse1)
-    return merged, state
+    return (_core_forward_bf16 if mode == CORE_BF16 else _core_forward_f32)(qkv, geo, wconv, pool, cls_row)
 
 
 def nystrom_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdtype, dt_code, pool,
@@ -473,130 +424,204 @@ def nystrom_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdt
     ``xn`` (bf16 class-row layer): the q block of dqkv is NOT written; qrows = (Aq, Xs), the
     operands of the q part's two small products (tm_cls_q_rows), else qrows = None.
     A geometry other than (64, 256): dmerged, merged and qkv are fp32 (``_nysg_core_backward``)."""
-    if (geo.dh, geo.nl) != (DH, NL):
+    mode = core_mode(geo, dt_code)
+    if mode == CORE_GENERIC:
         if cls_row is not None:
             raise NotImplementedError("the class-row layer runs at dim_head=64, num_landmarks=256 only")
-        return _nysg_core_backward(dmerged, merged, qkv, state, geo, wconv, tdtype, dt_code, pool, dwconv_out,
-                                   scale), None
+        return _nysg_core_backward(dmerged, merged, qkv, state, geo, wconv, tdtype, dt_code, pool, dwconv_out, scale)
+    if mode == CORE_BF16:
+        return _core_backward_bf16(dmerged, merged, qkv, state, geo, wconv, pool, dwconv_out, scale, cls_row, xn)
+    return _core_backward_f32(dmerged, merged, qkv, state, geo, wconv, pool, dwconv_out, scale, cls_row)
+
+
+def _core_landmarks(qkv, geo: Geometry, pool, T, code, st):
+    """The first stage of both MFMA cores: the landmark means of q and k (fp32) and their T copies."""
+    ql, kl = (pool(geo.nbh * NL * DH).view(geo.nbh, NL, DH) for _ in "qk")
+    ql_t, kl_t = (pool(geo.nbh * NL * DH, T).view(geo.nbh, NL, DH) for _ in "qk")
+    with probe("landmarks"):
+        _lib.call("tm_nys_landmarks", code, _p(qkv[0]), _p(qkv[1]), geo.nbh, geo.n, _p(ql), _p(kl), _p(ql_t),
+                  _p(kl_t), st)
+    return ql, kl, ql_t, kl_t
+
+
+def _core_a1_forward(qkv, kl_t, y_t, wconv, geo: Geometry, pool, T, code, cls_row, st):
+    """The last stage of both MFMA cores: merged [B, n, h*64] (T) and the A1 log-sum-exp (``cls_row``: that row)."""
     n, nbh, nh = geo.n, geo.nbh, geo.heads
-    q, k, v = qkv[0], qkv[1], qkv[2]
-    st = _stream()
-    mat = nbh * NL * NL
-    prec = 1 if dt_code == BF16 else 0
-    y_t = state["y_t"]
-    dk = pool(nbh * n * DH)
-    dkl = pool(nbh * NL * DH).view(nbh, NL, DH)
-    dy = pool(nbh * NL * DH).view(nbh, NL, DH)
-    dqkv_early = None
-    fused = state["a2s"] is not None     # bf16 mode: the A3 backward writes the final k / v parts
+    merged = pool(geo.B * n * nh * DH, T).view(geo.B, n, nh * DH)
+    lse1 = pool(nbh * n)
     if cls_row is not None:
-        # one non-zero query row: dq row, rank-1 dk~ / dY, the conv33 dv window (clsrow.hip); the
-        # bf16 consumers read only that row / window, the fp32 path reads dense zero-filled buffers
-        alloc = pool if fused else (lambda numel: torch.zeros(numel, dtype=torch.float32, device=q.device))
-        dq = alloc(nbh * n * DH)
-        dv = pool(nbh * n * DH, tdtype) if fused else alloc(nbh * n * DH)   # dv in T (the fused A3 reads bf16)
-        _lib.call("tm_cls_a1_row_bwd", dt_code, _p(dmerged), _p(q), _p(v), _p(state["kl_t"]), _p(y_t),
-                  _p(state["lse1"]), _p(wconv), geo.B, nh, n, cls_row, _p(dq), _p(dkl), _p(dy), _p(dv),
-                  _p(dwconv_out), st)
+        _lib.call("tm_cls_a1_row_fwd", code, _p(qkv[0]), _p(qkv[2]), _p(kl_t), _p(y_t), _p(wconv), nbh, nh, n,
+                  cls_row, _p(merged), _p(lse1), st)
     else:
-        # conv33 backward + D1
-        # bf16 mode: dq goes straight into the q part of dqkv as bf16 (tm_nys_a1_bwd_dqkv); the
-        # landmark term is added there in place at the end (tm_nys_assemble_q_slab_inplace)
-        dqkv_early = pool(geo.B * n * 3 * nh * DH, tdtype).view(geo.B, n, 3 * nh * DH) if fused else None
-        dq = None if fused else pool(nbh * n * DH)
-        dv = pool(nbh * n * DH, tdtype)      # the conv backward's dv in T (bf16 mode: read once by the fused A3)
+        with probe("a1_fwd"):
+            _lib.call("tm_nys_a1_fwd", code, _p(qkv[0]), _p(qkv[2]), _p(kl_t), _p(y_t), _p(wconv), nbh, nh, n,
+                      _p(merged), _p(lse1), st)
+    return merged, lse1
+
+
+def _core_forward_bf16(qkv, geo: Geometry, wconv, pool, cls_row):
+    """nystrom_core_forward, the bf16 step: q, k, v and merged bf16; the key-split A3 forward also
+    writes A2, and the pseudo-inverse chain runs on its split bf16 hi / lo planes (pinv_split.hip)."""
+    n, nbh, T, st = geo.n, geo.nbh, torch.bfloat16, _stream()
+    ql, kl, ql_t, kl_t = _core_landmarks(qkv, geo, pool, T, BF16, st)
+    a2 = pool(nbh * NL * NL).view(nbh, NL, NL)
+    a2s = pool(nbh * NL * NL)   # A2's hi + lo bf16 planes = one fp32 matrix's bytes
+    w, y = (pool(nbh * NL * DH).view(nbh, NL, DH) for _ in "wy")
+    lse3 = pool(nbh * NL)
+    work = pool(_lib.query("tm_nys_a3_workspace", nbh, n) // 4)
+    # (measured: running A3 V on a second stream beside the pseudo-inverse chain slowed the step -- the
+    #  chain's launches then wait for CUs -- so the path stays serial; the A3 partials' combine runs
+    #  inside the chain's last launch, on the CUs it leaves idle)
+    with probe("a3_fwd"):
+        _lib.call("tm_nys_a3_fwd_sim2", _p(ql), _p(kl), _p(qkv[1]), _p(qkv[2]), nbh, n, _p(work), _p(a2), _p(a2s), st)
+    saved = pool(_lib.query("tm_pinv_split_saved_floats", nbh, PINV_ITERS))
+    with probe("pinv_fwd"):
+        _lib.call("tm_pinv_fwd_split_a3", _p(a2), _p(a2s), nbh, PINV_ITERS, _p(saved), _p(work),
+                  _lib.query("tm_nys_a3_partials", nbh, n), _p(w), _p(lse3), st)
+    z = saved[:nbh * NL * NL].view(nbh, NL, NL)
+    y_t = pool(nbh * NL * DH, T)        # Y = Z W and its bf16 operand copy from the same launch
+    bmm([bmm_job(z, 0, w, 0, y, NL, DH, NL, Ct=y_t, ct_mode=1)], nbh, 1)
+    merged, lse1 = _core_a1_forward(qkv, kl_t, y_t, wconv, geo, pool, T, BF16, cls_row, st)
+    return merged, dict(ql=ql, kl=kl, ql_t=ql_t, kl_t=kl_t, a2=a2, a2s=a2s, pinv=saved, z=z, w=w, lse3=lse3, y=y,
+                        y_t=y_t, lse1=lse1)
+
+
+def _core_forward_f32(qkv, geo: Geometry, wconv, pool, cls_row):
+    """nystrom_core_forward, the fp32 parity step: everything fp32 on the exact kernels, one launch
+    per stage of App. A (same state keys; the T copies are fp32 too, y_t is y, no split planes)."""
+    n, nbh, T, st = geo.n, geo.nbh, torch.float32, _stream()
+    ql, kl, ql_t, kl_t = _core_landmarks(qkv, geo, pool, T, F32, st)
+    a2 = pool(nbh * NL * NL).view(nbh, NL, NL)
+    w, y = (pool(nbh * NL * DH).view(nbh, NL, DH) for _ in "wy")
+    lse3 = pool(nbh * NL)
+    work = pool(_lib.query("tm_nys_a3_workspace", nbh, n) // 4)
+    with probe("a3_fwd"):
+        _lib.call("tm_nys_a3_fwd", F32, _p(ql), _p(qkv[1]), _p(qkv[2]), nbh, n, _p(work), _p(w), _p(lse3), st)
+    saved = pool(_lib.query("tm_pinv_saved_floats", nbh, PINV_ITERS))
+    _lib.call("tm_nys_sim2_softmax", _p(ql), _p(kl), nbh, _p(a2), st)
+    _lib.call("tm_pinv_fwd", _p(a2), nbh, PINV_ITERS, 0, _p(saved), st)
+    z = saved[PINV_ITERS * nbh * NL * NL:(PINV_ITERS + 1) * nbh * NL * NL].view(nbh, NL, NL)
+    bmm([bmm_job(z, 0, w, 0, y, NL, DH, NL)], nbh, 0)
+    merged, lse1 = _core_a1_forward(qkv, kl_t, y, wconv, geo, pool, T, F32, cls_row, st)
+    return merged, dict(ql=ql, kl=kl, ql_t=ql_t, kl_t=kl_t, a2=a2, a2s=None, pinv=saved, z=z, w=w, lse3=lse3, y=y,
+                        y_t=y, lse1=lse1)
+
+
+def _core_backward_bf16(dmerged, merged, qkv, state, geo: Geometry, wconv, pool, dwconv_out, scale, cls_row, xn):
+    """nystrom_core_backward, the bf16 step: the A1 backward writes dq straight into dqkv, the fused
+    A3 backward its k / v parts; the q part has three endings (below)."""
+    n, nbh, nh, T, st = geo.n, geo.nbh, geo.heads, torch.bfloat16, _stream()
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    y_t, lse1, mat = state["y_t"], state["lse1"], nbh * NL * NL
+    dkl, dy, dw, dql = (pool(nbh * NL * DH).view(nbh, NL, DH) for _ in range(4))
+    dz, ds2 = (pool(mat).view(nbh, NL, NL) for _ in range(2))
+    d3 = pool(2 * nbh * NL)
+    # in bf16: the conv backward's dv and dW's copy (both read once, by the fused A3 backward), dqkv
+    dv, dw_t = pool(nbh * n * DH, T), pool(nbh * NL * DH, T)
+    dqkv = pool(geo.B * n * 3 * nh * DH, T).view(geo.B, n, 3 * nh * DH)
+    if cls_row is not None:
+        # class-row layer: one non-zero query row -- dq row, rank-1 dk~ / dY, the conv33 dv window
+        # (clsrow.hip); the consumers below read only that row / window
+        dq = pool(nbh * n * DH)
+        _lib.call("tm_cls_a1_row_bwd", BF16, _p(dmerged), _p(q), _p(v), _p(state["kl_t"]), _p(y_t), _p(lse1),
+                  _p(wconv), geo.B, nh, n, cls_row, _p(dq), _p(dkl), _p(dy), _p(dv), _p(dwconv_out), st)
+    else:
+        # conv33 backward + D1, then the A1 product backward: dq goes straight into the q part of
+        # dqkv as bf16; the landmark term is added there in place at the end
         d1 = pool(nbh * n)
         with defer_reductions(), probe("conv_bwd"):
             work = pool(_lib.query("tm_nys_conv_bwd_workspace", geo.B, nh, n) // 4)
-            _lib.call("tm_nys_conv_bwd", dt_code, _p(dmerged), _p(merged), _p(v), _p(wconv), nbh, nh, n, _p(dv),
+            _lib.call("tm_nys_conv_bwd", BF16, _p(dmerged), _p(merged), _p(v), _p(wconv), nbh, nh, n, _p(dv),
                       _p(d1), _p(work), _p(dwconv_out), _rq(), st)
-        # A1 product backward: dq (complete), dkl, dY
-        qpw = 256                    # geo.n is a multiple of 256 (Geometry)
-        work = pool(_lib.query("tm_nys_a1_bwd_workspace", nbh, n, qpw) // 4)
-        with defer_reductions():     # its dk~ and dY slab sums as one launch
-            with probe("a1_bwd"):
-                if fused:
-                    _lib.call("tm_nys_a1_bwd_dqkv", _p(q), _p(dmerged), _p(state["kl_t"]), _p(y_t), _p(state["lse1"]),
-                              _p(d1), nbh, nh, n, _p(dqkv_early), C.c_float(scale), _p(work), _p(dkl), _p(dy), _rq(), st)
-                else:
-                    _lib.call("tm_nys_a1_bwd", dt_code, _p(q), _p(dmerged), _p(state["kl_t"]), _p(y_t),
-                              _p(state["lse1"]), _p(d1), nbh, nh, n, qpw, _p(dq), _p(work), _p(dkl), _p(dy), 0, _rq(),
-                              st)
+        work = pool(_lib.query("tm_nys_a1_bwd_workspace", nbh, n, 256) // 4)   # 256 | geo.n (Geometry)
+        with defer_reductions(), probe("a1_bwd"):     # its dk~ and dY slab sums as one launch
+            _lib.call("tm_nys_a1_bwd_dqkv", _p(q), _p(dmerged), _p(state["kl_t"]), _p(y_t), _p(lse1), _p(d1),
+                      nbh, nh, n, _p(dqkv), C.c_float(scale), _p(work), _p(dkl), _p(dy), _rq(), st)
         flush_reductions()
-    # Y = Z W
-    dz = pool(mat).view(nbh, NL, NL)
-    dw = pool(nbh * NL * DH).view(nbh, NL, DH)
-    pwork = None
-    if state["a2s"] is not None:
-        # the split bf16 hi / lo planes of dZ (work[0] of tm_pinv_bwd_split) from the same launch
-        pwork = pool(_lib.query("tm_pinv_bwd_split_workspace_floats", nbh))
-        dz_job = bmm_job(dy, 0, state["w"], 1, dz, NL, NL, DH, Ct=pwork, ct_mode=2, ct_plane=mat)
-    else:
-        dz_job = bmm_job(dy, 0, state["w"], 1, dz, NL, NL, DH)
-    # dW = Z^T dY with, from the same launch, its T copy (the A3 backward's dO) and D3 =
-    # rowsum(dW o W) as the two 32-column partials the A3 backward sums
-    d3 = pool(2 * nbh * NL)
-    if dt_code == BF16:
-        dw_t = pool(nbh * NL * DH, tdtype)
-        dw_job = bmm_job(state["z"], 1, dy, 0, dw, NL, DH, NL, Ct=dw_t, ct_mode=1)
-    else:
-        dw_t = dw
-        dw_job = bmm_job(state["z"], 1, dy, 0, dw, NL, DH, NL)
+    # Y = Z W, one launch: dZ with its split bf16 hi / lo planes (work[0] of tm_pinv_bwd_split); dW = Z^T dY with
+    # its bf16 copy (the A3 backward's dO) and D3 = rowsum(dW o W) as the two 32-column partials that backward sums
+    pwork = pool(_lib.query("tm_pinv_bwd_split_workspace_floats", nbh))
+    dw_job = bmm_job(state["z"], 1, dy, 0, dw, NL, DH, NL, Ct=dw_t, ct_mode=1)
     dw_job.Rd, dw_job.Rw = d3.data_ptr(), state["w"].data_ptr()
-    bmm([dz_job, dw_job], nbh, prec)
-    dql3 = pool(nbh * NL * DH).view(nbh, NL, DH)
+    bmm([bmm_job(dy, 0, state["w"], 1, dz, NL, NL, DH, Ct=pwork, ct_mode=2, ct_plane=mat), dw_job], nbh, 1)
     work3 = pool(_lib.query("tm_nys_a3_bwd_workspace", nbh, n) // 4)
-    if not fused:
-        # A3 product backward: dk (=), dv (+=), dql3 (=)
-        with probe("a3_bwd"):
-            _lib.call("tm_nys_a3_bwd", dt_code, _p(state["ql_t"]), _p(dw_t), _p(k), _p(v), _p(state["lse3"]),
-                      _p(d3), nbh, nh, n, _p(dk), _p(dv), _p(work3), _p(dql3), 0, _rq(), st)
-    # pseudo-inverse backward -> dA2, then softmax backward
-    ds2 = pool(mat).view(nbh, NL, NL)
-    if state["a2s"] is not None:
-        # split operands; the softmax backward is fused into the chain's last launch
-        with probe("pinv_bwd"):
-            _lib.call("tm_pinv_bwd_split", _p(state["a2"]), _p(state["a2s"]), nbh, PINV_ITERS, _p(state["pinv"]),
-                      _p(pwork), 1, _p(ds2), st)
+    # pseudo-inverse backward on the split operands; the softmax backward is fused into its last launch
+    with probe("pinv_bwd"):
+        _lib.call("tm_pinv_bwd_split", _p(state["a2"]), _p(state["a2s"]), nbh, PINV_ITERS, _p(state["pinv"]),
+                  _p(pwork), 1, _p(ds2), st)
+    # dq~ (landmark path, without the A3 part) and the final dk~ (+= the A1 part) first; the fused
+    # A3 backward then writes k / v of dqkv and dq~3
+    bmm([bmm_job(ds2, 0, state["kl"], 0, dql, NL, DH, NL),
+         bmm_job(ds2, 1, state["ql"], 0, dkl, NL, DH, NL, E1=dkl, e1=1.0)], nbh, 1)
+    lo, hi = (0, n) if cls_row is None else (max(cls_row - 16, 0), min(cls_row + 17, n))   # dv's non-zero rows
+    with probe("a3_bwd"):
+        # dql = NULL: the dq~3 partial slab stays in work3; the q part's launch below sums it in place
+        _lib.call("tm_nys_a3_bwd_fused", _p(state["ql_t"]), _p(dw_t), _p(k), _p(v), _p(state["lse3"]), _p(d3),
+                  nbh, nh, n, _p(dv), lo, hi, _p(dkl), _p(work3), None, _p(dqkv), _rq(), st)
+    slabs = _lib.query("tm_nys_a3_bwd_slabs", nbh, n)
+    if cls_row is None:     # dense layer: the landmark term added in place to the dq the A1 backward wrote
+        _lib.call("tm_nys_assemble_q_slab_inplace", _p(dql), _p(work3), slabs, geo.B, nh, n, C.c_float(scale),
+                  _p(dqkv), st)
+    elif xn is None:        # class-row layer, dense q block: the class row's dq plus the landmark term
+        _lib.call("tm_nys_assemble_q_slab", BF16, _p(dq), cls_row, _p(dql), _p(work3), slabs, geo.B, nh, n,
+                  C.c_float(scale), _p(dqkv), st)
+    else:                   # class-row layer, q block left unwritten: the operands of its two small products
+        Aq, Xs = (h.view(geo.B, QROWS, nh * DH) for h in pool(2 * geo.B * QROWS * nh * DH).chunk(2))
+        with probe("cls_q_rows"):
+            _lib.call("tm_cls_q_rows", _p(dql), _p(work3), slabs, _p(dq), _p(xn), geo.B, nh, n, cls_row, _p(Aq),
+                      _p(Xs), st)
+        return dqkv, (Aq, Xs)
+    return dqkv, None
+
+
+def _core_backward_f32(dmerged, merged, qkv, state, geo: Geometry, wconv, pool, dwconv_out, scale, cls_row):
+    """nystrom_core_backward, the fp32 parity step: one launch per stage, dense fp32 dq / dk / dv
+    put together by tm_nys_assemble_dqkv (no qrows)."""
+    n, nbh, nh, st = geo.n, geo.nbh, geo.heads, _stream()
+    q, k, v = qkv[0], qkv[1], qkv[2]
+    y, lse1, mat = state["y"], state["lse1"], nbh * NL * NL
+    dk = pool(nbh * n * DH)
+    dkl, dy, dw, dql3, dql = (pool(nbh * NL * DH).view(nbh, NL, DH) for _ in range(5))
+    dz, da2, ds2 = (pool(mat).view(nbh, NL, NL) for _ in range(3))
+    d3 = pool(2 * nbh * NL)
+    dqkv = pool(geo.B * n * 3 * nh * DH).view(geo.B, n, 3 * nh * DH)
+    if cls_row is not None:
+        # class-row layer: one non-zero query row -- dq row, rank-1 dk~ / dY, the conv33 dv window
+        # (clsrow.hip).  The consumers below are the dense kernels, which read whole buffers, so dq
+        # and dv are zero-filled and only that row / window is written
+        dq, dv = (torch.zeros(nbh * n * DH, dtype=torch.float32, device=q.device) for _ in range(2))
+        _lib.call("tm_cls_a1_row_bwd", F32, _p(dmerged), _p(q), _p(v), _p(state["kl_t"]), _p(y), _p(lse1),
+                  _p(wconv), geo.B, nh, n, cls_row, _p(dq), _p(dkl), _p(dy), _p(dv), _p(dwconv_out), st)
     else:
-        da2 = pool(mat).view(nbh, NL, NL)
-        pwork = pool(_lib.query("tm_pinv_bwd_workspace_floats", nbh))
-        _lib.call("tm_pinv_bwd", _p(state["a2"]), nbh, PINV_ITERS, prec, _p(state["pinv"]), _p(dz), _p(pwork),
-                  _p(da2), st)
-        _lib.call("tm_softmax_bwd_rows256", _p(state["a2"]), _p(da2), _p(ds2), nbh * NL, st)
-    dql = pool(nbh * NL * DH).view(nbh, NL, DH)
-    dqkv = None if cls_row is None and fused else pool(geo.B * n * 3 * nh * DH, tdtype).view(geo.B, n, 3 * nh * DH)
-    if dqkv is None:
-        dqkv = dqkv_early
-    if fused:
-        # dq~ (landmark path, without the A3 part) and the final dk~ (+= the A1 part) first; the
-        # fused A3 backward then writes k / v of dqkv and dq~3; assemble_q writes q
-        bmm([bmm_job(ds2, 0, state["kl"], 0, dql, NL, DH, NL),
-             bmm_job(ds2, 1, state["ql"], 0, dkl, NL, DH, NL, E1=dkl, e1=1.0)], nbh, prec)
-        with probe("a3_bwd"):
-            lo, hi = (0, n) if cls_row is None else (max(cls_row - 16, 0), min(cls_row + 17, n))
-            # dql = NULL: the dq~3 partial slab stays in work3; assemble_q_slab sums it in place
-            _lib.call("tm_nys_a3_bwd_fused", _p(state["ql_t"]), _p(dw_t), _p(k), _p(v), _p(state["lse3"]), _p(d3),
-                      nbh, nh, n, _p(dv), lo, hi, _p(dkl), _p(work3), None, _p(dqkv), _rq(), st)
-        slabs = _lib.query("tm_nys_a3_bwd_slabs", nbh, n)
-        if cls_row is None:
-            _lib.call("tm_nys_assemble_q_slab_inplace", _p(dql), _p(work3), slabs, geo.B, nh, n, C.c_float(scale),
-                      _p(dqkv), st)
-        elif xn is not None:
-            qr = pool(2 * geo.B * QROWS * nh * DH)
-            Aq, Xs = qr[:geo.B * QROWS * nh * DH].view(geo.B, QROWS, nh * DH), qr[geo.B * QROWS * nh * DH:].view(
-                geo.B, QROWS, nh * DH)
-            with probe("cls_q_rows"):
-                _lib.call("tm_cls_q_rows", _p(dql), _p(work3), slabs, _p(dq), _p(xn), geo.B, nh, n, cls_row, _p(Aq),
-                          _p(Xs), st)
-            return dqkv, (Aq, Xs)
-        else:
-            _lib.call("tm_nys_assemble_q_slab", dt_code, _p(dq), cls_row, _p(dql), _p(work3), slabs, geo.B, nh, n,
-                      C.c_float(scale), _p(dqkv), st)
-        return dqkv, None
+        # conv33 backward + D1, then the A1 product backward: dq (complete), dk~, dY
+        dq, dv, d1 = pool(nbh * n * DH), pool(nbh * n * DH), pool(nbh * n)
+        with defer_reductions(), probe("conv_bwd"):
+            work = pool(_lib.query("tm_nys_conv_bwd_workspace", geo.B, nh, n) // 4)
+            _lib.call("tm_nys_conv_bwd", F32, _p(dmerged), _p(merged), _p(v), _p(wconv), nbh, nh, n, _p(dv),
+                      _p(d1), _p(work), _p(dwconv_out), _rq(), st)
+        work = pool(_lib.query("tm_nys_a1_bwd_workspace", nbh, n, 256) // 4)   # query rows per workgroup: 256 | geo.n
+        with defer_reductions(), probe("a1_bwd"):     # its dk~ and dY slab sums as one launch
+            _lib.call("tm_nys_a1_bwd", F32, _p(q), _p(dmerged), _p(state["kl_t"]), _p(y), _p(lse1), _p(d1),
+                      nbh, nh, n, 256, _p(dq), _p(work), _p(dkl), _p(dy), 0, _rq(), st)
+        flush_reductions()
+    # Y = Z W: dZ = dY W^T; dW = Z^T dY with, from the same launch, D3 = rowsum(dW o W) as the two
+    # 32-column partials the A3 backward sums
+    dw_job = bmm_job(state["z"], 1, dy, 0, dw, NL, DH, NL)
+    dw_job.Rd, dw_job.Rw = d3.data_ptr(), state["w"].data_ptr()
+    bmm([bmm_job(dy, 0, state["w"], 1, dz, NL, NL, DH), dw_job], nbh, 0)
+    # A3 product backward: dk (=), dv (+=), dql3 (=)
+    work3 = pool(_lib.query("tm_nys_a3_bwd_workspace", nbh, n) // 4)
+    with probe("a3_bwd"):
+        _lib.call("tm_nys_a3_bwd", F32, _p(state["ql_t"]), _p(dw), _p(k), _p(v), _p(state["lse3"]), _p(d3),
+                  nbh, nh, n, _p(dk), _p(dv), _p(work3), _p(dql3), 0, _rq(), st)
+    # pseudo-inverse backward -> dA2, then the row-softmax backward
+    pwork = pool(_lib.query("tm_pinv_bwd_workspace_floats", nbh))
+    _lib.call("tm_pinv_bwd", _p(state["a2"]), nbh, PINV_ITERS, 0, _p(state["pinv"]), _p(dz), _p(pwork), _p(da2), st)
+    _lib.call("tm_softmax_bwd_rows256", _p(state["a2"]), _p(da2), _p(ds2), nbh * NL, st)
+    # dq~ (+= the A3 part) and dk~ (+= the A1 part), then q / k / v into dqkv
     bmm([bmm_job(ds2, 0, state["kl"], 0, dql, NL, DH, NL, E1=dql3, e1=1.0),
-         bmm_job(ds2, 1, state["ql"], 0, dkl, NL, DH, NL, E1=dkl, e1=1.0)], nbh, prec)
-    _lib.call("tm_nys_assemble_dqkv", dt_code, _p(dq), _p(dql), _p(dk), _p(dkl), _p(dv), geo.B, nh, n,
+         bmm_job(ds2, 1, state["ql"], 0, dkl, NL, DH, NL, E1=dkl, e1=1.0)], nbh, 0)
+    _lib.call("tm_nys_assemble_dqkv", F32, _p(dq), _p(dql), _p(dk), _p(dkl), _p(dv), geo.B, nh, n,
               C.c_float(scale), _p(dqkv), st)
     return dqkv, None
 
@@ -642,7 +667,7 @@ def _nysg_core_forward(qkv, geo: Geometry, wconv, pool):
 
 
 def _nysg_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdtype, dt_code, pool, dwconv_out, scale):
-    """Backward of _nysg_core_forward: dmerged, merged, qkv fp32 -> dqkv [B, n, 3*h*dh] (T);
+    """Backward of _nysg_core_forward: dmerged, merged, qkv fp32 -> (dqkv [B, n, 3*h*dh] (T), None);
     writes dwconv_out."""
     n, nbh, nh, dh, nl = geo.n, geo.nbh, geo.heads, geo.dh, geo.nl
     q, k, v = qkv[0], qkv[1], qkv[2]
@@ -691,7 +716,7 @@ def _nysg_core_backward(dmerged, merged, qkv, state, geo: Geometry, wconv, tdtyp
     dqkv = pool(geo.B * n * 3 * nh * dh, tdtype).view(geo.B, n, 3 * nh * dh)
     _lib.call("tm_nysg_assemble_dqkv", dh, nl, dt_code, _p(dq), _p(dql), _p(dk), _p(dkl), _p(dv), geo.B, nh, n,
               C.c_float(scale), _p(dqkv), st)
-    return dqkv
+    return dqkv, None
 
 
 # ----------------------------------------------------------------------------- TransLayer
@@ -739,7 +764,7 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
     st = _stream()
     # each weight gradient shares its data gradient's launch (bf16 step, 512-wide geometry only);
     # pair_gemms: True (the pairs of PAIR_SITES), False, or the names to pair
-    on = dt_code == BF16 and (geo.dh, geo.nl) == (DH, NL)
+    on = core_mode(geo, dt_code) == CORE_BF16
     names = PAIR_SITES if pair_gemms is True else (pair_gemms or ())
     pair_out, pair_qkv, pair_kv = (on and k in names for k in ("out", "qkv", "kv"))
     if saved["cls_only"]:
@@ -768,8 +793,7 @@ def translayer_backward(dH, H_in, saved, geo: Geometry, prm, grads, tdtype, dt_c
                 gemm(dout, prm["wo"], dmerged, B * n, D, D, lda=D, ldb=D, ldc=D, b_kn=1, dtype=dt_code)
     # bf16 class-row layer: q reaches the loss only through its landmark means and the class row, so
     # the q part of to_qkv's backward runs as two small products on tm_cls_q_rows' operands
-    qrows_on = (CLS_Q_ROWS and saved["cls_only"] and dt_code == BF16 and saved["core"]["a2s"] is not None
-                and "wqkv_f32" in prm)
+    qrows_on = CLS_Q_ROWS and saved["cls_only"] and on and "wqkv_f32" in prm
     dqkv, qrows = nystrom_core_backward(dmerged, saved["merged"], saved["qkv"], saved["core"], geo, prm["wconv"],
                                         tdtype, dt_code, pool, grads["wconv"], DH ** -0.5,
                                         cls_row=pad if saved["cls_only"] else None,
@@ -829,6 +853,29 @@ FC1_RCC2048 = {"main": "_fc1.3", "inner": ("_fc1.0", "_fc1.2")}               # 
 FC1_EMBED = {"main": None, "inner": None}
 
 
+def _cast(w, tdtype, dt_code, pool):
+    """The T copy of one fp32 tensor by its own launch (fp32 mode: the tensor itself)."""
+    if dt_code == F32:
+        return w.contiguous()
+    out = pool(w.numel(), tdtype)
+    _lib.call("tm_cast_f32", dt_code, _p(w.contiguous()), _p(out), w.numel(), _stream())
+    return out.view(w.shape)
+
+
+def _fill_cast_table(tab, srcs, tdtype, pool):
+    """Enter the contiguous fp32 tensors ``srcs`` (kept alive by the caller until the launch that takes
+    the table and casts them all) and fresh T copies into the CastTable ``tab``; returns the copies."""
+    outs, off = [], 0
+    for i, w in enumerate(srcs):
+        o = pool(w.numel(), tdtype).view(w.shape)
+        tab.src[i], tab.dst[i], tab.offset[i] = w.data_ptr(), o.data_ptr(), off
+        off += w.numel()
+        outs.append(o)
+    tab.count = len(srcs)
+    tab.offset[len(srcs)] = off
+    return outs
+
+
 class TransMILEngine:
     """Fused TransMIL forward / backward, heads = 8, dim_head = 64, 256 landmarks.
 
@@ -854,31 +901,6 @@ class TransMILEngine:
         self.cls_only = cls_only
         _lib.lib()
 
-    def _cast(self, w, pool):
-        if self.dt_code == F32:
-            return w.contiguous()
-        out = pool(w.numel(), self.tdtype)
-        _lib.call("tm_cast_f32", self.dt_code, _p(w.contiguous()), _p(out), w.numel(), _stream())
-        return out.view(w.shape)
-
-    def _cast_many(self, ws, pool):
-        """T copies of several fp32 weights in one launch (fp32 mode: the weights themselves)."""
-        ws = [w.contiguous() for w in ws]
-        if self.dt_code == F32:
-            return ws
-        tab = _lib.CastTable()
-        tab.count = len(ws)
-        outs = []
-        off = 0
-        for i, w in enumerate(ws):
-            o = pool(w.numel(), self.tdtype).view(w.shape)
-            tab.src[i], tab.dst[i], tab.offset[i] = w.data_ptr(), o.data_ptr(), off
-            off += w.numel()
-            outs.append(o)
-        tab.offset[len(ws)] = off
-        _lib.call("tm_cast_f32_many", self.dt_code, C.byref(tab), _stream())
-        return outs
-
     def prepare(self, params, pool, x2d=None, counter=None, seed_out=None, cls_rows=None):
         """fp32 master parameters -> the per-call operand set (T copies of the GEMM weights and,
         when given, of the bag ``x2d``), the folded PPEG kernel, and the dropout counter
@@ -893,27 +915,16 @@ class TransMILEngine:
             ws.append(params[main + ".weight"])
         if inner is not None:
             ws.append(params[inner[0] + ".weight"])
+        # the preparation launch casts (bf16 mode; fp32: an empty table) whole 4-element pieces: a bag
+        # whose B*N*F is not a multiple of 4 (odd in_features) is cast by its own launch instead
         tab = _lib.CastTable()
-        if self.dt_code == F32:
-            outs = [w.contiguous() for w in ws]
-            p["xt"] = None if x2d is None else x2d.contiguous()
+        x_in_table = self.dt_code != F32 and x2d is not None and x2d.numel() % 4 == 0
+        srcs = [w.contiguous() for w in ws] + ([x2d.contiguous()] if x_in_table else [])
+        outs = srcs if self.dt_code == F32 else _fill_cast_table(tab, srcs, self.tdtype, pool)
+        if x_in_table:
+            p["xt"] = outs.pop()
         else:
-            # the preparation launch casts whole 4-element pieces: a bag whose B*N*F is not a
-            # multiple of 4 (odd in_features) is cast by its own launch instead
-            x_in_table = x2d is not None and x2d.numel() % 4 == 0
-            srcs = [w.contiguous() for w in ws] + ([x2d.contiguous()] if x_in_table else [])
-            outs, off = [], 0
-            for i, w in enumerate(srcs):
-                o = pool(w.numel(), self.tdtype).view(w.shape)
-                tab.src[i], tab.dst[i], tab.offset[i] = w.data_ptr(), o.data_ptr(), off
-                off += w.numel()
-                outs.append(o)
-            tab.count = len(srcs)
-            tab.offset[len(srcs)] = off
-            if x_in_table:
-                p["xt"] = outs.pop()
-            else:
-                p["xt"] = None if x2d is None else self._cast(x2d, pool)
+            p["xt"] = None if x2d is None else _cast(x2d, self.tdtype, self.dt_code, pool)
         wqkv1, wo1, wqkv2, wo2 = outs[:4]
         if main is not None:
             p["w1"] = outs[4]
@@ -1165,13 +1176,6 @@ class NystromEngine:
         self.dt_code = BF16 if dtype == torch.bfloat16 else F32
         _lib.lib()
 
-    def _cast(self, w, pool):
-        if self.dt_code == F32:
-            return w.contiguous()
-        out = pool(w.numel(), self.tdtype)
-        _lib.call("tm_cast_f32", self.dt_code, _p(w.contiguous()), _p(out), w.numel(), _stream())
-        return out.view(w.shape)
-
     def forward(self, x, wqkv, wo, bo, wconv, heads, drop_p=0.0, seed=0, seed_dev=None, dim_head=DH,
                 num_landmarks=NL):
         B, S, D = x.shape
@@ -1181,16 +1185,12 @@ class NystromEngine:
                                       f"with dim == heads * dim_head (got {(dh, nl)}, dim={D}, heads={heads})")
         generic = (dh, nl) != (DH, NL)   # the fp32 tm_nysg_* core: q, k, v and merged stay fp32
         pool = Pool(x.device)
-        geo = Geometry(B, max(S - 1, 1), D, D, heads, dh, nl)
-        geo.S = S
-        geo.n = ((S + nl - 1) // nl) * nl
-        geo.pad = geo.n - S
-        geo.l = geo.n // nl
+        geo = Geometry.for_sequence(B, S, D, heads, dh, nl)
         n, pad = geo.n, geo.pad
         xc = x.reshape(B * S, D).contiguous()
         xp = pool(B * n * D, self.tdtype).view(B, n, D)
         _lib.call("tm_pad_rows", self.dt_code, _p(xc), B, S, n, pad, D, _p(xp), _stream())
-        wqkv_t, wo_t = self._cast(wqkv, pool), self._cast(wo, pool)
+        wqkv_t, wo_t = (_cast(w, self.tdtype, self.dt_code, pool) for w in (wqkv, wo))
         qdtype = torch.float32 if generic else self.tdtype
         qkv = pool(3 * geo.nbh * n * dh, qdtype).view(3, geo.nbh, n, dh)
         gemm(xp, wqkv_t, qkv, B * n, 3 * D, D, lda=D, ldb=D, ldc=0, dtype=self.dt_code,
