@@ -23,8 +23,11 @@
 // addend matrices, and up to four outputs (split, fp32, and two split side outputs).
 // Entry sequence of a workgroup (grid (nbh, 16, njobs): head, tile, job, no division): four wide
 // scalar loads bring the job descriptor (SJob, three 64-B lines) and the launch-wide scalars into
-// SGPRs; the lane's own address arithmetic runs under them; one wait; the producers issue chunk 0,
-// then (waves 4-7, which also own an epilogue piece) the plain loads of the epilogue addends, then
+// SGPRs; the lane's own address arithmetic runs under them; the producers of a product job issue
+// chunk 0 of term 0, still under them, from the kernel's leading arguments (`meta` and term 0's operand
+// pointers of every job: 14 dwords that are preloaded into SGPRs at wave start, so chunk 0's cold
+// round trip no longer queues behind the descriptor's); one wait; then (waves 4-7, which also own an
+// epilogue piece) the plain loads of the epilogue addends, then
 // chunk 1.  Nothing after the wait loads from the kernel argument again: the walk and the epilogue's
 // store sequence run on SGPRs ("The pseudo-inverse chain", has the measured table).
 //
@@ -325,6 +328,14 @@ TM_DEV void lane_addresses(int wv, int lane, const char* smem, unsigned (&pre)[N
   }
 }
 
+// A producer wave's PPW pieces (8 image rows each) of one plane chunk by LDS-DMA: `base` is the
+// chunk's first element in the plane, `img` the wave's rows of the ring slot, kr the image kind.
+TM_DEV void issue_pieces(const bf16* base, int kr, const unsigned (&pre)[NPRE], char* img) {
+#pragma unroll
+  for (int i = 0; i < PPW; ++i)
+    __builtin_amdgcn_global_load_lds((glb_t*)(base + (kr ? pre[PPW + i] : pre[i])), (lds_t*)(img + i * 1024), 16, 0, 0);
+}
+
 // Roles: waves 0-3 are consumers (one 32x32 subtile each, the whole K: LDS reads + MFMAs +
 // epilogue), waves 4-7 producers (wave 4+p issues plane p of every chunk by LDS-DMA: 0 A hi,
 // 1 A lo, 2 B hi, 3 B lo).  One s_barrier per chunk: a chunk is read after the barrier that
@@ -395,24 +406,18 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
     const int o0w = pl < 2 ? m0 : n0;
     const bf16* const pb0 = op0.p + hoff + ((pl & 1) ? plane : 0);
     const bf16* const pb1 = op1.p + hoff + ((pl & 1) ? plane : 0);
-    unsigned loff[2][PPW];  // [kr][piece]: row * 256 + 8 * (slot ^ swizzle(row)) (lane_addresses)
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) { loff[0][i] = pre[i]; loff[1][i] = pre[PPW + i]; }
+    // pre[kr * PPW + piece]: row * 256 + 8 * (slot ^ swizzle(row)) (lane_addresses)
     auto issue = [&](int c) {
       char* img = smem + (c % NSLOT) * SLOT + pl * PC + rb * 128;
       const int t = c >> 2, k0 = (c & 3) * 64;
       const int kr = t ? op1.kr : op0.kr;
-      const bf16* base = (t ? pb1 : pb0) + (kr ? k0 * NL + o0w : o0w * NL + k0);
-#pragma unroll
-      for (int i = 0; i < PPW; ++i)
-        __builtin_amdgcn_global_load_lds((glb_t*)(base + (kr ? loff[1][i] : loff[0][i])), (lds_t*)(img + i * 1024),
-                                         16, 0, 0);
+      issue_pieces((t ? pb1 : pb0) + (kr ? k0 * NL + o0w : o0w * NL + k0), kr, pre, img);
     };
-    // Chunk 0 goes out first.  The addend loads of the producers that own an epilogue piece sit
+    // Chunk 0 is already out: the kernel issued it ahead of the descriptor's wait, from its preloaded
+    // arguments.  The addend loads of the producers that own an epilogue piece sit
     // between chunk 0 and chunk 1: the first counted wait below leaves exactly chunk 1's PPW DMAs
-    // outstanding, so it retires chunk 0 wherever the compiler places those plain loads (ahead of
-    // chunk 0, between the chunks or behind chunk 1), and every later wait is behind them.
-    issue(0);
+    // outstanding, so it retires chunk 0 wherever the compiler places those plain loads (between the
+    // chunks or behind chunk 1), and every later wait is behind them.
     __builtin_amdgcn_sched_barrier(0);
     if (epi) load_addends();
     __builtin_amdgcn_sched_barrier(0);
@@ -540,8 +545,20 @@ TM_DEV void stage_tile(const SJob& J, int nbh, long long plane, const float* max
 // first DMA).
 // AUX: the launch carries the A3 combine row (only the forward's last level; a separate
 // instantiation, so the other levels' code is not touched by the combine's registers)
+//
+// Leading arguments (the translation unit is built with -amdgpu-kernarg-preload-count=14, csrc/Makefile:
+// the 14 dwords ahead of L are in SGPRs when a wave starts, without a load): what chunk 0 of the ring
+// needs and blockIdx does not give.  aN / bN = L.j[N].a[0].p / L.j[N].b[0].p; `meta` (stage_meta):
+//   bits 0-1 njobs, bits 2 + 3N .. 4 + 3N job N: is a product, a[0].kr, b[0].kr, bits 11-31 nbh.
+// A row that is not a product (the abs-sum job, the AUX row blockIdx.z == njobs) has no bit set.
+// Launcher::go derives all of them from L; L stays the only source of every other field.
+constexpr int META_JOB = 2, META_NBH = 2 + 3 * MAXJ, META_NBH_MAX = (1 << (32 - META_NBH)) - 1;
+constexpr int L_OFF = 64;   // of L in the kernel-argument segment: 7 leading arguments (56 B), alignas(64)
+static_assert(alignof(SLaunch) == L_OFF && 8 + 6 * sizeof(void*) <= L_OFF, "kernel-argument offset of L");
+
 template <bool AUX, bool DOT = false>
-__global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
+__global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(unsigned meta, const bf16* a0, const bf16* b0, const bf16* a1,
+                                                              const bf16* b1, const bf16* a2, const bf16* b2, SLaunch L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long t0 = 0, t1 = 0;
 #ifdef TM_DIAG
@@ -565,7 +582,7 @@ __global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
   u32x8_t rs;
   {
     typedef const __attribute__((address_space(4))) char kchar;
-    kchar* kp = (kchar*)__builtin_amdgcn_kernarg_segment_ptr();
+    kchar* kp = (kchar*)__builtin_amdgcn_kernarg_segment_ptr() + L_OFF;
     kchar* jp = kp + (size_t)min((int)blockIdx.z, MAXJ - 1) * sizeof(SJob);
     asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dwordx16 %2, %4, 0x80\n\t"
                  "s_load_dwordx8 %3, %5, %6"
@@ -573,7 +590,25 @@ __global__ __launch_bounds__(NTHREADS) void pinv_stage_kernel(SLaunch L) {
                  : "s"(jp), "s"(kp), "n"(MAXJ * sizeof(SJob)));
   }
   unsigned pre[NPRE];
-  lane_addresses(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6), threadIdx.x & 63, smem, pre);
+  const int wv0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  lane_addresses(wv0, threadIdx.x & 63, smem, pre);
+  // Chunk 0 of term 0 leaves here, under the descriptor's round trip, from the preloaded arguments and
+  // blockIdx alone (the same addresses stage_tile's issue(0) formed from the descriptor; plane is
+  // nbh * MAT, Launcher::go requires it).  Rows that are not products issue nothing.
+  {
+    const unsigned zj = blockIdx.z;
+    const unsigned jb = zj < (meta & 3u) ? (meta >> (META_JOB + 3 * zj)) & 7u : 0u;
+    if (wv0 >= 4 && (jb & 1u)) {
+      const int p = wv0 - 4, pl = p / (NPROD / 4), rb = (p % (NPROD / 4)) * PPW * 8;
+      const bf16* src = pl < 2 ? (zj == 0 ? a0 : (zj == 1 ? a1 : a2)) : (zj == 0 ? b0 : (zj == 1 ? b1 : b2));
+      const int kr = (jb >> (pl < 2 ? 1 : 2)) & 1;
+      const int o0w = pl < 2 ? (blockIdx.y >> 2) * 64 : (blockIdx.y & 3) * 64;
+      const long long plane0 = (long long)(meta >> META_NBH) * MAT;
+      issue_pieces(src + (size_t)blockIdx.x * MAT + ((pl & 1) ? plane0 : 0) + (kr ? o0w : o0w * NL), kr, pre,
+                   smem + pl * PC + rb * 128);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
   {
     u32x4_t pa = {pre[0], pre[1], pre[2], pre[3]}, pb = {pre[4], pre[5], pre[6], pre[7]};
     u32x2_t pc = {pre[8], pre[9]};
@@ -884,18 +919,32 @@ struct Launcher {
   }
   bool dot = false;   // the last job's e2 / cf carry the c-gradient dot (job_dotx / job_dot_part)
   void add(const SJob& j) { L.j[L.njobs++] = j; }
+  // the kernel's `meta` argument (see pinv_stage_kernel)
+  unsigned stage_meta() const {
+    unsigned m = (unsigned)L.njobs | ((unsigned)L.nbh << META_NBH);
+    for (int n = 0; n < L.njobs; ++n)
+      if (L.j[n].kind == KIND_PRODUCT)
+        m |= (1u | (L.j[n].a[0].kr ? 2u : 0u) | (L.j[n].b[0].kr ? 4u : 0u)) << (META_JOB + 3 * n);
+    return m;
+  }
   int go(hipStream_t st) {
+    // the kernel issues its first chunk before it has the descriptor: the lo planes are at nbh * MAT
+    TM_REQUIRE(L.njobs >= 1 && L.njobs <= MAXJ && L.nbh >= 1 && L.nbh <= META_NBH_MAX, "pinv stage: njobs 1..3, nbh < 2^21");
+    TM_REQUIRE(L.plane == (long long)L.nbh * MAT, "pinv stage: plane must be nbh * 65536");
     dim3 grid(L.nbh, 16, L.njobs);
+    const unsigned meta = stage_meta();
+    const bf16 *a0 = L.j[0].a[0].p, *b0 = L.j[0].b[0].p, *a1 = L.j[1].a[0].p, *b1 = L.j[1].b[0].p, *a2 = L.j[2].a[0].p,
+               *b2 = L.j[2].b[0].p;
     if (L.a3.w) {   // one more row for the A3 combine: ceil(nbh * 32 / 3) <= 16 nbh items
       grid.z += 1;
       tm_allow_smem(pinv_stage_kernel<true>, STAGE_LDS + EPI_LDS);
-      pinv_stage_kernel<true><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(L);
+      pinv_stage_kernel<true><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(meta, a0, b0, a1, b1, a2, b2, L);
     } else if (dot) {   // the backward's last level: the c-gradient dot in its epilogue
       tm_allow_smem(pinv_stage_kernel<false, true>, STAGE_LDS + EPI_LDS);
-      pinv_stage_kernel<false, true><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(L);
+      pinv_stage_kernel<false, true><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(meta, a0, b0, a1, b1, a2, b2, L);
     } else {
       tm_allow_smem(pinv_stage_kernel<false>, STAGE_LDS + EPI_LDS);
-      pinv_stage_kernel<false><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(L);
+      pinv_stage_kernel<false><<<grid, NTHREADS, STAGE_LDS + EPI_LDS, st>>>(meta, a0, b0, a1, b1, a2, b2, L);
     }
     TM_CHECK_LAUNCH();
 #ifdef TM_DIAG
